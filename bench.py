@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the PLS fit hot path on MI355X: NIPALS components/sec + achieved HBM GB/s.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one complete fit (A components) of BASELINE.json config 3 -- synthetic tall
@@ -10,13 +10,22 @@ region.  With N > 1 the SAME matrix is row-sharded over the ranks (strong scalin
 is quoted at n = 1M for 1/2/4/8 GPUs), one process per GPU, the K x M / (K+1)-length partial
 products all-reduced with torch.distributed (RCCL over xGMI).  Rank 0 prints ONE JSON line.
 
-Extra objects on that line:
+A plain run sets up, warms up, times the K steps and prints the line; `ms_per_step` is the
+wall time of one timed step.  Extra objects on that line:
   roofline      dominant kernel family of the timed fits: algorithmic bytes per launch / average
                 launch duration (HIP events on the launch stream, recorded by the library while
-                the timed steps run) against the 8.0 TB/s HBM3E peak.
+                the timed steps run) against the 8.0 TB/s HBM3E peak.  At N > 1 it takes
+                profiled steps of its own after the timed region: with --full only.
+With --full, after the timed steps:
   cpu_baseline  the oracle's C restatement of the reference algorithm (Eigen is unavailable,
                 so this is "kind": "port"), one host core, on a bounded row sample.
-  alt           the other execution plans on the same data (not the headline value).
+  alt           the other execution plans on the same data (not the headline value); at N > 1
+                alt.rccl, a short leg under the library's RCCL reducer.
+
+--dump-outputs DIR writes what the last timed step returned (W, P, Q, R, B in fp64; T in the
+workload's dtype, a fixed seeded sample of its rows when there are more than DUMP_T_ROWS) as
+DIR/<name>.npy; rank 0's shard at N > 1.  The inputs are generated from a fixed seed, so two
+builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -25,6 +34,8 @@ import json
 import os
 import sys
 import time
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
@@ -67,6 +78,8 @@ WORKLOADS.update({
 })
 TIGHT_LD = {"C3odd-", "C3odd+", "C4odd"}  # leading dimension = N (no padding to 16 bytes)
 PAD_LD = {"C3a8pad": 64, "C3pad": 64}      # leading dimension = N + this many elements
+# rows of the scores --dump-outputs writes (T is 160 MB at config 3): at most 20 MB of outputs in all for every workload above
+DUMP_T_ROWS = 65536
 
 
 def parse():
@@ -102,7 +115,15 @@ def parse():
                     "line is printed without it")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--cpu-rows", type=int, default=1 << 20, help="rows of the CPU baseline sample (default: the whole workload, ~10 s on one core)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the alternative plans, the stand-alone deflation and the CPU baselines "
+                         "(N = 1), the RCCL leg and the roofline's profiled steps (N > 1); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (rank 0)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def timed_fits(h, torch, dist, world, X, Y, A, steps, warmup, out):
@@ -125,6 +146,20 @@ def timed_fits(h, torch, dist, world, X, Y, A, steps, warmup, out):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
     return el, h.timing()
+
+
+def output_snapshot(torch, out):
+    """Host copies of what a fit returned: W, P, Q, R, B (fp64) and T (the workload's dtype; rows sorted from a fixed seeded
+    sample of DUMP_T_ROWS when it has more)."""
+    snap = {}
+    for k, v in out.items():
+        if v is None:
+            continue
+        if k == "T" and v.shape[0] > DUMP_T_ROWS:
+            rows = np.sort(np.random.default_rng(0).choice(v.shape[0], DUMP_T_ROWS, replace=False))
+            v = v.index_select(0, torch.from_numpy(rows).to(v.device))
+        snap[k] = v.contiguous().cpu().numpy()
+    return snap
 
 
 def pmc_traffic(workload, algo, fuse, family):
@@ -373,7 +408,7 @@ def main():
     # HIP events around every streaming launch (the roofline figures).  At N = 1 they bracket the launches of the
     # timed steps themselves; the brackets cost ~8 us per component (0.5 % of a single-GPU component, but 4 % of a
     # 1/8-size one), so at N > 1 the timed steps run without them and the roofline comes from extra profiled steps
-    # after the timed region.
+    # after the timed region (--full only).
     after = world > 1 or a.profile_after
     h.set_option(pls_amd.OPT_PROFILE, 0 if after else 1)
     out = None
@@ -383,13 +418,18 @@ def main():
         out["Q"] = pls_amd.colmajor_empty(M, A, f64, X.device, ld=M)
         out["B"] = pls_amd.colmajor_empty(K, M, f64, X.device, ld=K)
         out["T"] = pls_amd.colmajor_empty(nrows, A, tdt, X.device, ld=nrows)
+    dumped = None
+
     def measure(out):
+        nonlocal dumped
         out = h.fit_device(X, Y, A, out=out)  # allocates outputs + workspace once
         torch.cuda.synchronize()
         h.set_option(pls_amd.OPT_PROFILE, 0 if after else 1)
         el, tm = timed_fits(h, torch, dist, world, X, Y, A, a.steps, a.warmup, out)
+        if a.dump_outputs and rank == 0:  # (before any later fit overwrites `out`)
+            dumped = output_snapshot(torch, out)
         where = "timed steps"
-        if after:
+        if after and (a.full or a.profile_after):
             h.set_option(pls_amd.OPT_PROFILE, 1)
             _, tm = timed_fits(h, torch, dist, world, X, Y, A, min(a.steps, 3), 1, out)
             where = "separate profiled steps after the timed region (N > 1, or --profile-after)"
@@ -433,6 +473,10 @@ def main():
             reducer_used = "torch (the " + had + " reducer failed in the fits" + (": " + why[:300] if why else " on another rank") + ")"
             res = measure(None)
         out, el, tm, roofline_where = res
+    if dumped is not None:
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for k, v in dumped.items():
+            np.save(os.path.join(a.dump_outputs, k + ".npy"), v)
     value = A * a.steps / el
     es = 8 if dt == "f64" else 4
     line = {
@@ -457,9 +501,9 @@ def main():
         tr, src = pmc_traffic(a.workload, a.algo, a.fuse, line["roofline"]["kernel"])
         line["roofline"]["traffic"] = tr
         line["roofline"]["traffic_source"] = src
-    if rank == 0 or world > 1:
+    if a.full and world == 1:
         alt = {}
-        if not a.no_alt and world == 1:
+        if not a.no_alt:
             plans = {"kernel_fused": (0, 1), "kernel_unfused": (0, 0), "nipals_fused": (1, 1), "nipals_unfused": (1, 0)}
             if K <= 2048:
                 plans["gram_mfma_syrk"] = (2, 1)  # XX on the matrix cores + component loop on K x K + T = X R
@@ -531,7 +575,7 @@ def main():
             del W
         line["alt"] = alt
 
-    if (world > 1 or a.rccl_leg_at_one_rank) and not a.no_alt:
+    if ((a.full and world > 1) or a.rccl_leg_at_one_rank) and not a.no_alt:
         # The RCCL leg must never cost the run its line: if it does not finish in time (a communicator that hangs in its
         # set-up on one rank) rank 0 prints the headline as measured and every rank leaves.
         import threading
@@ -556,7 +600,7 @@ def main():
         line.setdefault("alt", {})["rccl"] = res
 
     if rank == 0:
-        if not a.no_cpu and world == 1:  # the CPU leg runs on rank 0 at N = 1 only
+        if a.full and not a.no_cpu and world == 1:  # the CPU leg runs on rank 0 at N = 1 only
             try:
                 base, omp = cpu_baseline(N, K, M, A, a.cpu_rows)
                 line["cpu_baseline"] = base

@@ -89,24 +89,18 @@ def test_row_partition():
         row_partition(10, 2, 2)
 
 
-REF_MAIN = "/root/reference/src/main.cpp"
+REF_MAIN = os.path.join(ROOT, "oracle", "_ref", "ref_main")  # built by `make -C oracle _ref` (build() runs it)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_MAIN), reason="the reference tree is not on this machine (GPU box)")
-def test_reference_main_builds_unchanged_against_this_header(tmp_path):
+def test_reference_main_builds_unchanged_against_this_header():
     """The strongest boundary check available without the reference's Eigen: its own CSV-driven main
     (src/main.cpp:1-44), UNCHANGED, compiles against include/PLS/pls.h and links against libpls.so -- every
     type, free function, enum value, constructor and member it uses exists here with a compatible signature."""
-    host = os.path.join(ROOT, "pls_amd", "host")
-    csrc = os.path.join(ROOT, "pls_amd", "csrc")
-    if not os.path.exists(os.path.join(host, "libpls.so")):
-        pytest.skip("libpls.so not built")
-    exe = str(tmp_path / "ref_main")
-    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "include"), REF_MAIN, "-o", exe,
-                        "-L", host, "-lpls", "-L", csrc, "-lpls_hip", "-L", "/opt/rocm/lib", "-lamdhip64",
-                        f"-Wl,-rpath,{host}", f"-Wl,-rpath,{csrc}", "-Wl,-rpath,/opt/rocm/lib"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    if os.path.exists(REF_MAIN + ".err"):
+        pytest.fail("the reference's src/main.cpp did not build against this header:\n" + open(REF_MAIN + ".err").read()[-3000:])
+    if not os.path.exists(REF_MAIN):
+        pytest.skip("oracle/_ref/ref_main not built: the reference tree was not there when the project was built")
+    exe = REF_MAIN
     # same usage behaviour as the reference (exit(100) on a wrong argument count, src/main.cpp:12-16); no GPU needed
     u = subprocess.run([exe], capture_output=True, text=True)
     assert u.returncode == 100

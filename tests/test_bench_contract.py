@@ -33,7 +33,7 @@ def test_roofline_helper_and_traffic_lookup():
 @pytest.mark.gpu
 def test_bench_prints_one_contract_line():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "3", "--warmup", "1",
-                        "--cpu-rows", "4096"], capture_output=True, text=True, timeout=600)
+                        "--cpu-rows", "4096", "--full"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, "exactly one JSON line on stdout"
@@ -48,6 +48,49 @@ def test_bench_prints_one_contract_line():
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in d["cpu_baseline"], k
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["cores"] == 1
+
+
+def test_output_snapshot_samples_the_scores():
+    """--dump-outputs: every returned array on the host in its own dtype; scores with more than DUMP_T_ROWS rows cut to a
+    fixed, seeded, sorted row sample (the same from run to run)."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    N, A = bench.DUMP_T_ROWS + 1000, 3
+    T = torch.arange(N * A, dtype=torch.float32).reshape(A, N).t()  # column-major, as the library returns it
+    out = {"W": torch.ones(7, A, dtype=torch.float64), "T": T, "B": None}
+    s1, s2 = bench.output_snapshot(torch, out), bench.output_snapshot(torch, out)
+    assert sorted(s1) == ["T", "W"] and s1["W"].dtype == np.float64 and s1["T"].dtype == np.float32
+    assert s1["T"].shape == (bench.DUMP_T_ROWS, A) and np.array_equal(s1["T"], s2["T"])
+    rows = s1["T"][:, 0].astype(np.int64)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(s1["T"][:, 2], rows + 2 * N)
+    small = bench.output_snapshot(torch, {"T": T[:100]})
+    assert np.array_equal(small["T"], T[:100].numpy())
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_headline_and_dumps_outputs(tmp_path, oracle, po):
+    """A plain run (no --full) prints the contract line without the extra legs; --dump-outputs writes what the last timed
+    step returned, which is the fit of the seeded synthetic inputs."""
+    import numpy as np
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, "exactly one JSON line on stdout"
+    d = json.loads(lines[0])
+    for k in REQUIRED:
+        assert k in d, k
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["roofline"]["measured_over"] == "timed steps"
+    assert "alt" not in d and "cpu_baseline" not in d
+    N, K, M, A = 4096, 64, 1, 5
+    got = {k: np.load(str(tmp_path / (k + ".npy"))) for k in "WPQRTB"}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert got["T"].shape == (N, A) and got["B"].shape == (K, M) and got["W"].shape == (K, A)
+    Xh, Yh = oracle.synth_x(0, N, K), oracle.synth_y(0, N, M)
+    ref = oracle.plsr(Xh, Yh, A)
+    assert po.rel_fro(got["B"], oracle.coefficients(ref["R"], ref["Q"])) < 1e-10
 
 
 @pytest.mark.gpu
@@ -69,7 +112,7 @@ def test_bench_two_ranks_as_the_driver_launches_it():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", "29571", os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "tiny", "--backend", "gloo"],
+                        "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "tiny", "--backend", "gloo", "--full"],
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]

@@ -21,7 +21,7 @@ pmc() {  # name, command...
 }
 for part in $PARTS; do case $part in
 c3)
-  python3 bench.py --steps 20 --warmup 5 > $E/bench_default_run.json 2> /dev/null
+  python3 bench.py --steps 20 --warmup 5 --full > $E/bench_default_run.json 2> /dev/null
   stats final_nipals_fused python3 bench.py --steps 5 --warmup 2 --no-alt --no-cpu
   pmc C3_nipals_fused python3 bench.py --steps 2 --warmup 1 --no-alt --no-cpu
   stats c3_kernel_fused python3 bench.py --algo kernel --steps 5 --warmup 2 --no-alt --no-cpu
@@ -43,7 +43,7 @@ deflate)
   stats deflate_piece python3 tools/deflate_run.py
   pmc deflate_piece python3 tools/deflate_run.py ;;
 c4)
-  python3 bench.py --workload C4 --steps 10 --warmup 3 --no-cpu > $E/bench_C4_all_plans.json 2> /dev/null
+  python3 bench.py --workload C4 --steps 10 --warmup 3 --no-cpu --full > $E/bench_C4_all_plans.json 2> /dev/null
   python3 bench.py --workload C4 --algo kernel --steps 10 --warmup 3 --no-cpu --no-alt > $E/bench_C4_kernel_plan.json 2> /dev/null
   stats c4_nipals python3 bench.py --workload C4 --steps 3 --warmup 1 --no-alt --no-cpu
   pmc C4_nipals_fused python3 bench.py --workload C4 --steps 2 --warmup 1 --no-alt --no-cpu

@@ -7,7 +7,7 @@ O=gpurun_out/r4; mkdir -p $O; rm -f $O/fixed_*
 for rep in 1 2 3; do
   python3 bench.py --workload C3eighth --steps 20 --warmup 5 --no-cpu --no-alt > $O/fixed_brackets_$rep.json 2>/dev/null
   python3 bench.py --workload C3eighth --steps 20 --warmup 5 --no-cpu --no-alt --profile-after > $O/fixed_plain_$rep.json 2>/dev/null
-  timeout -k 10 300 python3 bench.py --gpus 2 --backend gloo --reducer ipc --workload C3eighth --steps 20 --warmup 5 --no-cpu --no-alt > $O/fixed_ipc2_$rep.json 2> $O/fixed_ipc2_$rep.err
+  timeout -k 10 300 python3 bench.py --gpus 2 --backend gloo --reducer ipc --workload C3eighth --steps 20 --warmup 5 --no-cpu --no-alt --full > $O/fixed_ipc2_$rep.json 2> $O/fixed_ipc2_$rep.err
 done
 python3 - <<'PY'
 import glob, json, os

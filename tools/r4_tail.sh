@@ -9,7 +9,7 @@ PLS_HIP_TAIL=1 python3 tools/tail_ab.py > $O/tail_digest_1.txt 2> $O/tail_digest
 if cmp -s $O/tail_digest_0.txt $O/tail_digest_1.txt; then echo "tail A/B: bit-identical on $(wc -l < $O/tail_digest_1.txt) fits"; else echo "tail A/B: DIFFERENT"; diff $O/tail_digest_0.txt $O/tail_digest_1.txt; exit 1; fi
 for rep in 1 2; do for t in 0 1; do
   PLS_HIP_TAIL=$t python3 bench.py --workload C3eighth --steps 20 --warmup 5 --no-cpu --no-alt > $O/tail${t}_eighth_$rep.json 2>/dev/null
-  PLS_HIP_TAIL=$t timeout -k 10 300 python3 bench.py --gpus 2 --backend gloo --reducer ipc --workload C3eighth --steps 20 --warmup 5 --no-cpu --no-alt > $O/tail${t}_eighth_ipc2_$rep.json 2> $O/tail${t}_eighth_ipc2_$rep.err
+  PLS_HIP_TAIL=$t timeout -k 10 300 python3 bench.py --gpus 2 --backend gloo --reducer ipc --workload C3eighth --steps 20 --warmup 5 --no-cpu --no-alt --full > $O/tail${t}_eighth_ipc2_$rep.json 2> $O/tail${t}_eighth_ipc2_$rep.err
 done; done
 for t in 0 1; do
   PLS_HIP_TAIL=$t python3 bench.py --steps 10 --warmup 3 --no-cpu --no-alt > $O/tail${t}_C3.json 2>/dev/null

@@ -9,7 +9,7 @@ for rep in 1 2 3; do
   for t in 1 2; do
     PLS_HIP_TAIL=$t python3 bench.py --workload C3eighth --steps 20 --warmup 5 --no-cpu --no-alt --profile-after > $O/fixed_tail${t}_plain_$rep.json 2>/dev/null
     PLS_HIP_TAIL=$t python3 bench.py --workload C3eighth --algo kernel --steps 20 --warmup 5 --no-cpu --no-alt --profile-after > $O/fixed_tail${t}_kernelplan_$rep.json 2>/dev/null
-    PLS_HIP_TAIL=$t timeout -k 10 300 python3 bench.py --gpus 2 --backend gloo --reducer ipc --workload C3eighth --steps 20 --warmup 5 --no-cpu --no-alt > $O/fixed_tail${t}_ipc2_$rep.json 2> $O/fixed_tail${t}_ipc2_$rep.err
+    PLS_HIP_TAIL=$t timeout -k 10 300 python3 bench.py --gpus 2 --backend gloo --reducer ipc --workload C3eighth --steps 20 --warmup 5 --no-cpu --no-alt --full > $O/fixed_tail${t}_ipc2_$rep.json 2> $O/fixed_tail${t}_ipc2_$rep.err
   done
 done
 python3 - <<'PY'
