@@ -119,6 +119,11 @@ typedef enum {
  * PLS_HIP_REPLICA_GUARD=0, which must be set identically on EVERY rank, removes it).
  * KERNEL_TYPE2 / GRAM add one message of 8*K*K (X^T X); pls_hip_colwise_z_scores sends two
  * of 8*K, pls_hip_sse_by_components one of 8*A*M per range of component counts.
+ * pls_hip_cv_folds sends, in this order: the partition (8*nranks: each rank's row count in
+ * its own slot); on its batched route X^T X (8*K*K) and X^T Y (8*K*M) of all rows; the
+ * held-out rows (8*rows*(K+M) per message of whole folds, rows*(K+M) capped at 2^20 unless a
+ * single fold is larger); then E (8*len per piece of at most 2^20 of its values) on the
+ * batched route, or the messages of one KERNEL_TYPE1 fit per fold on the refit route.
  * Return 0 on success.
  */
 #define PLS_HIP_REDUCE_SLICES 8
@@ -241,8 +246,20 @@ PLS_HIP_API int pls_hip_model_sse(pls_hip_handle h, const void *X, int64_t ldx, 
  * XX - X_test^T X_test applied on the fly (the KERNEL_TYPE2 recurrence, src/pls.cpp:422-425): no per-fold
  * pass over X.  Small single-response data (N <= 1024, K <= 26 * floor(16 / ceil(N/64)), M = 1) run as one single-launch fit per
  * fold on the masked X instead (no X^T X at all).  Shapes that launch declines (M > 32, A > 4096, K > 16384, workspaces that do not fit) run as one
- * device refit per fold instead -- same results, num_folds fits.  Single rank.  The call returns after the work
+ * device refit per fold instead -- same results, num_folds fits.  The call returns after the work
  * has completed.
+ * Row-sharded handle (a reducer installed, pls_hip_set_reducer): the call is a COLLECTIVE.  Every rank calls it
+ * with the same K, M, A, test_idx, test_size, num_folds and dtype; X, Y are the rank's own block of N rows
+ * (N may be 0), blocks contiguous in rank order (rank r owns global rows [sum_{s<r} N_s, + N_r), as
+ * pls_amd.distributed.row_partition makes them), and test_idx holds GLOBAL row indices in [0, n_total).  The
+ * library learns the partition from one message of the ranks' N; the checks on global data (an index out of
+ * range, n_total < 2, test_size >= n_total: a fold leaving no training rows) run after it, so every rank returns
+ * the same PLS_HIP_ERR_INVALID; checks on local data (pointers, ld) run before it, as in the sharded fit.  Every
+ * rank receives the full E, bit-identical on all ranks.  The batched route (never the single-launch routes, which
+ * read every row) sums X^T X and X^T Y over the ranks and runs a contiguous range of the folds on each rank; the
+ * refit route runs one sharded fit per fold, every rank on its own training rows.  A workspace that does not fit
+ * on any rank fails the call on every rank (PLS_HIP_ERR_ALLOC) instead of falling back to the refit route.
+ * PLS_HIP_CV_REFIT must be set alike on every rank.
  */
 PLS_HIP_API int pls_hip_cv_folds(pls_hip_handle h, const void *X, int64_t ldx, const void *Y, int64_t ldy,
                                  int64_t N, int64_t K, int64_t M, int64_t A, const int64_t *test_idx,

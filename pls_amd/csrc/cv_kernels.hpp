@@ -24,6 +24,47 @@ __global__ __launch_bounds__(WG) void cv_gather_kernel(const T *__restrict__ X, 
     for (int m = threadIdx.x; m < M; m += WG) Yt[(i64)blockIdx.x * M + m] = (double)Y[row + (i64)m * ldy];
 }
 
+// ---- row-sharded handles: the held-out rows of every fold to every rank (pls_hip.hip cv_folds_sharded) ----
+// A message of rows j = 0..nrow-1 of the list idx (GLOBAL row numbers), K + M values each (x_j, then y_j), as RED_SLICES
+// slices of L = nrow * (K + M): the rank that owns row idx[j] (rows [row0, row0 + N)) writes it into slice 0, every other
+// value of every rank is zero -- each sum over ranks and slices has exactly one non-zero term.   grid = nrow workgroups.
+template <typename T>
+__global__ __launch_bounds__(WG) void cv_pack_test_rows_kernel(const T *__restrict__ X, i64 ldx, const T *__restrict__ Y, i64 ldy,
+                                                               int K, int M, const i64 *__restrict__ idx, i64 row0, i64 N,
+                                                               double *__restrict__ red, i64 L) {
+    const i64 j = blockIdx.x, row = idx[j] - row0;
+    const bool own = row >= 0 && row < N;
+    const int KM = K + M;
+    double *out = red + j * KM;
+    for (int c = threadIdx.x; c < KM; c += WG) {
+        double v = 0.0;
+        if (own) v = c < K ? (double)X[row + (i64)c * ldx] : (double)Y[row + (i64)(c - K) * ldy];
+        out[c] = v;
+#pragma unroll
+        for (int s = 1; s < RED_SLICES; ++s) out[(i64)s * L + c] = 0.0;
+    }
+}
+
+// ... and the summed message into the rows of the batched kernel's layout: Xt[o*K + k], Yt[o*M + m] for o = 0..nrow-1
+__global__ __launch_bounds__(WG) void cv_unpack_test_rows_kernel(const double *__restrict__ red, i64 L, int K, int M,
+                                                                 double *__restrict__ Xt, double *__restrict__ Yt) {
+    const int KM = K + M;
+    for (i64 j = (i64)blockIdx.x * WG + threadIdx.x; j < L; j += (i64)gridDim.x * WG) {
+        double s = 0.0;
+#pragma unroll
+        for (int i = 0; i < RED_SLICES; ++i) s += red[(i64)i * L + j];
+        const i64 o = j / KM;
+        const int c = (int)(j - o * KM);
+        if (c < K) Xt[o * K + c] = s;
+        else Yt[o * M + (c - K)] = s;
+    }
+}
+
+// the partition message: value `v` (this rank's row count) in slot `slot` of slice 0, zeros in the other RED_SLICES * n - 1
+__global__ __launch_bounds__(WG) void cv_slot_kernel(double *__restrict__ red, int n, int slot, double v) {
+    for (int j = threadIdx.x; j < RED_SLICES * n; j += WG) red[j] = j == slot ? v : 0.0;
+}
+
 // per-fold workspace layout (doubles)
 struct CvLayout {
     i64 xy, w, p, r, q, red, v, u, yh, total;
@@ -43,18 +84,19 @@ struct CvLayout {
 };
 
 // E[m][obs + c*nobs], obs = fold*ts + i, nobs = folds*ts.  Dynamic LDS: A doubles.
+// Workgroup b runs fold fold0 + b (a rank of a sharded handle runs a contiguous range of the folds); Xt / Yt hold the test
+// rows of ALL folds, ws one workspace per workgroup.
 __global__ __launch_bounds__(UPD_THREADS) void cv_folds_kernel(
     const double *__restrict__ XX, const double *__restrict__ XY, const double *__restrict__ Xt,
     const double *__restrict__ Yt, int K, int M, int A, int ts, double *__restrict__ ws,
-    double *__restrict__ E, int power_iters) {
+    double *__restrict__ E, int power_iters, int fold0, i64 nobs) {
     extern __shared__ double cs[];
     __shared__ UpdShared sh;
     __shared__ double ttred[UPD_WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int f = blockIdx.x;
-    const i64 nobs = (i64)gridDim.x * ts;
+    const int f = fold0 + (int)blockIdx.x;
     const CvLayout L(K, M, A, ts);
-    double *base = ws + (i64)f * L.total;
+    double *base = ws + (i64)blockIdx.x * L.total;
     double *XYf = base + L.xy, *Wf = base + L.w, *Pf = base + L.p, *Rf = base + L.r, *Qf = base + L.q;
     double *red1 = base + L.red, *v = base + L.v, *u = base + L.u, *yh = base + L.yh;
     const double *xt = Xt + (i64)f * ts * K, *yt = Yt + (i64)f * ts * M;

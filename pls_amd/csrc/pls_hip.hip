@@ -101,7 +101,7 @@ int pls_hip_destroy(pls_hip_handle h) {
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
     DevBuf *bufs[] = {&h->tailcnt, &h->resident, &h->rgflags, &h->zeros, &h->part, &h->sspart, &h->xbpart, &h->wide1, &h->red, &h->red2, &h->xx, &h->xyp, &h->praw, &h->xy, &h->v, &h->cs, &h->coop, &h->lm, &h->gxx, &h->gxy, &h->tab,
-                      &h->cvidx, &h->cvx, &h->cvy, &h->cvws, &h->cve, &h->cvtx, &h->cvty, &h->cvtt, &h->cvm, &h->cvkeep, &h->work, &h->hX, &h->hY,
+                      &h->cvidx, &h->cvx, &h->cvy, &h->cvws, &h->cve, &h->cvtx, &h->cvty, &h->cvtt, &h->cvm, &h->cvkeep, &h->cvred, &h->work, &h->hX, &h->hY,
                       &h->hT, &h->hW, &h->hP, &h->hQ, &h->hR, &h->hB, &h->hIn, &h->hOut};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
@@ -501,7 +501,15 @@ int pls_hip_cv_folds(pls_hip_handle h, const void *X, int64_t ldx, const void *Y
     CHK(check_handle(h));
     if (dtype != PLS_HIP_F64 && dtype != PLS_HIP_F32) return fail(h, PLS_HIP_ERR_INVALID, "bad dtype");
     if (mem != PLS_HIP_MEM_HOST && mem != PLS_HIP_MEM_DEVICE) return fail(h, PLS_HIP_ERR_INVALID, "bad mem kind");
-    if (h->reducer) return fail(h, PLS_HIP_ERR_UNSUPPORTED, "cv_folds: not available on a sharded handle");
+    if (h->reducer) {  // a collective: local checks here, the ones on global data after the partition message
+        if (N < 0 || K < 1 || M < 1 || A < 1 || A > K || K > (1 << 30) || (N > 0 && (!X || !Y)) || !test_idx || !E ||
+            test_size < 1 || num_folds < 1 || ldx < std::max<i64>(N, 1) || ldy < std::max<i64>(N, 1) ||
+            num_folds > (1 << 22) || test_size > (1 << 20))
+            return fail(h, PLS_HIP_ERR_INVALID, "bad cv_folds arguments");
+        if (M > plsk::LM_MAX) return fail(h, PLS_HIP_ERR_UNSUPPORTED, "more than 1024 responses not supported on the device");
+        CHK(set_device(h));
+        return cv_folds_sharded(h, X, ldx, Y, ldy, N, K, M, A, test_idx, test_size, num_folds, dtype, mem, E);
+    }
     if (N < 2 || K < 1 || M < 1 || A < 1 || A > K || K > (1 << 30) || !X || !Y ||
         !test_idx || !E || test_size < 1 || test_size >= N || num_folds < 1 || ldx < N || ldy < N ||
         num_folds > (1 << 22) || test_size > (1 << 20))

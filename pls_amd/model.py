@@ -278,7 +278,10 @@ class Handle:
     def cv_folds(self, X, Y, A: int, test_idx):
         """Residuals of batched cross-validation folds (cv_LOO / cv_LSO of the reference in one launch).
         test_idx: (num_folds, test_size) integer array of held-out rows.  Returns E with shape (M, nobs, A),
-        nobs = num_folds * test_size: E[m] is what Residual.errors()[m] holds."""
+        nobs = num_folds * test_size: E[m] is what Residual.errors()[m] holds.
+        On a row-sharded handle (attach_reducer / attach_ipc_exchange) the call is a collective: every rank calls it with
+        its own block of rows (possibly none) and the same A and test_idx, whose entries are GLOBAL row indices (blocks
+        contiguous in rank order, as pls_amd.distributed.row_partition makes them); every rank receives the full E."""
         idx = np.ascontiguousarray(np.asarray(test_idx, dtype=np.int64))
         if idx.ndim == 1:
             idx = idx[:, None]
@@ -299,7 +302,7 @@ class Handle:
         M = Y.shape[1]
         E = np.zeros((M, A, nf * ts))
         p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-        rc = self._lib.pls_hip_cv_folds(self.h, p(X), N, p(Y), N, N, K, M, A, p(idx), ts, nf,
+        rc = self._lib.pls_hip_cv_folds(self.h, p(X), max(N, 1), p(Y), max(N, 1), N, K, M, A, p(idx), ts, nf,
                                         L.F64 if dt == np.float64 else L.F32, L.MEM_HOST, p(E))
         L.check(rc, self.h)
         return E.transpose(0, 2, 1)
