@@ -94,9 +94,12 @@ typedef enum {
     PLS_HIP_OPT_PROFILE = 3,    /* HIP events on the launch stream: 1 = around the streaming kernels over X, 2 = around every kernel */
     PLS_HIP_OPT_POWER_ITERS = 4, /* squarings of the S^T S power iteration (m > 1); default 48 */
     PLS_HIP_OPT_FUSED_GRID = 5,  /* workgroups of the fused pass; 0 (default) = 2 per CU */
-    PLS_HIP_OPT_WORK_LAYOUT = 6, /* NIPALS work buffer (the deflated copy of X) of a fused fit: 1 (default) row-tile-major, 0 column-major */
+    PLS_HIP_OPT_WORK_LAYOUT = 6, /* NIPALS work buffer (the deflated copy of X) of a fused fit: 1 (default) row-tile-major, 0 column-major.
+                                    The buffer is scratch of the library, not an output: the last component's pass deflates in
+                                    registers only, so after a fused fit of A components it holds X_{A-2} */
     PLS_HIP_OPT_DEFER = 7,       /* NIPALS plan, K <= 512: write the deflated matrix back every D-th component only (1..4); the
-                                    D - 1 pending rank-1 updates are re-applied in registers.  1 (default) = explicit deflation */
+                                    D - 1 pending rank-1 updates are re-applied in registers.  1 (default) = explicit deflation:
+                                    every X_a that a later pass reads is materialised (the last one, which none reads, is not) */
     PLS_HIP_OPT_GRAPH = 8        /* 1: a device-memory pls_hip_fit that repeats an earlier call (same pointers, shapes, options) is
                                     captured into a hipGraph on its second occurrence and replayed as ONE graph launch from the
                                     third on.  Single rank, profiling off, a stream of its own (not the default stream).  0 (default): every

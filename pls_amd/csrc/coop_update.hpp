@@ -217,6 +217,9 @@ __global__ __launch_bounds__(COOP_WG) void coop_update_kernel(const double *__re
     grid_exchange(cntB, G);
     // every workgroup has passed exchange 1: its counter can be zeroed for the next launch
     if (wg == 0 && tid == 0) __hip_atomic_exchange(cntA, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // (the prologue launch has no c_j, but the unrolled recurrence below reads cs[0] against rv = 0: whatever an earlier kernel
+    // left in this LDS -- a NaN or Inf pattern -- would turn r_0 into NaN)
+    if (n == 0 && tid == 0) cs[0] = 0.0;
     for (int j0 = 0; j0 < n; j0 += COOP_CH) {
         const int nv = min(COOP_CH, n - j0);
         const double ct = gather_totals(cpart + (i64)j0 * G, nv, G, lbuf);

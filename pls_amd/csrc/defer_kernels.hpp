@@ -1,7 +1,8 @@
 // Deferred write-back of the rank-1 deflation (opt-in: PLS_HIP_OPT_DEFER = D > 1; NIPALS plan, K <= 512).
 //
-// The explicit NIPALS plan materialises X_a = X_{a-1} - t_{a-1} p_{a-1}^T in HBM for every component (one read +
-// one write of X per component).  Here up to D rank-1 updates stay PENDING: a pass loads the last stored matrix
+// The explicit NIPALS plan materialises X_a = X_{a-1} - t_{a-1} p_{a-1}^T in HBM for every component that a later pass
+// reads (one read + one write of X per component; like the plan here it skips the store of the LAST component's matrix,
+// which nothing reads: fused_pass_kernel's STORE = false).  Here up to D rank-1 updates stay PENDING: a pass loads the last stored matrix
 // X_b, applies the pending updates (t_b, p_b) ... (t_{a-1}, p_{a-1}) to the tile in registers -- the same fused
 // multiply-adds, rounded to the storage type after each one, so the tile holds exactly the bits the explicit plan
 // would have stored -- computes t_a and X_a^T t_a from it, and writes X_a back only when D updates are pending.

@@ -420,8 +420,12 @@ struct TileWalk<true, R> {
 // ONEWG: a read-only pass at 16 or fewer columns per lane compiled for ONE workgroup per CU (its default is two, 5 % faster
 // on a long sweep): the form that may sum its partial rows -- and run the one-response update -- in its own tail, which is
 // what a SHORT pass wants (below ~1.5 GB the two launches behind the pass cost more than the 5 %).
+// STORE = false (DEFL only): the LAST deflating pass of a fit -- X_{A-1} is read by no later launch, so the tile is deflated in
+// registers (the same FMA, the same rounding to T: scores and loadings come from the same bits) and goes nowhere: no
+// destination descriptor, no stores, no pacing (that exists for the read/write mix only); dst is not touched.  Grid, tile
+// walk and XCD weights are those of the storing pass, so every workgroup sums the same tiles in the same order.
 template <typename T, int V, int R, int NT, int CPT, bool DEFL, int LDAUX_ = AUX_NT, int STAUX = AUX_NT, bool RDST = false,
-          int EDGE = 0, bool TILED = false, bool ONEWG = false>
+          int EDGE = 0, bool TILED = false, bool ONEWG = false, bool STORE = true>
 __global__ __launch_bounds__(NT, (NT / 256) * ((CPT <= 16 && !DEFL && !ONEWG) ? 2 : 1)) void fused_pass_kernel(
     const T *X, i64 ldx, i64 tsx, T *dst, i64 ldd, i64 tsd, i64 N, int K,  // dst may alias X (in-place deflation)
     const double *__restrict__ v, const T *__restrict__ tprev, const double *__restrict__ pprev,
@@ -435,6 +439,7 @@ __global__ __launch_bounds__(NT, (NT / 256) * ((CPT <= 16 && !DEFL && !ONEWG) ? 
     constexpr int LDAUX = (EDGE == 2) ? 0 : LDAUX_;
     static_assert(RP <= WAVE && WAVE % RP == 0 && NT % RP == 0, "tile shape");
     static_assert(!TILED || (EDGE == 0 && !RDST), "the tiled copy is aligned and keeps one tile shape");
+    static_assert(STORE || (DEFL && !RDST), "only a deflating pass has a store side to drop; without it there is no destination tile shape");
     // LDS: the operand vectors v [CG*CPT] and, when DEFL, p_prev [CG*CPT], the score exchange, the block-sum
     // scratch.  One static block with a fixed layout (p_prev first): the instruction schedule of the headline
     // kernel turned out to depend on these addresses (1.3 % slower with the vectors after the exchange buffer or
@@ -484,7 +489,7 @@ __global__ __launch_bounds__(NT, (NT / 256) * ((CPT <= 16 && !DEFL && !ONEWG) ? 
     constexpr int CGD = EDGE ? WAVE / RP : CG;
     const int cgw = EDGE ? __builtin_amdgcn_readfirstlane(cg) : 0;
     const uint32_t xoff = (uint32_t)(((i64)rp * V + (i64)(cg - cgw) * ldx) * (i64)sizeof(T));
-    uint32_t doff = DEFL ? (uint32_t)(((i64)rp * V + (i64)cg * ldd) * (i64)sizeof(T)) : 0u;
+    uint32_t doff = (DEFL && STORE) ? (uint32_t)(((i64)rp * V + (i64)cg * ldd) * (i64)sizeof(T)) : 0u;
     i64 dtile = tsd;  // destination elements per source tile
     if constexpr (RDST && DEFL) {
         // the lane's rows rp*V.. fall into sub-tile (rp*V)/rdst of the R/rdst destination tiles a source tile covers
@@ -519,7 +524,7 @@ __global__ __launch_bounds__(NT, (NT / 256) * ((CPT <= 16 && !DEFL && !ONEWG) ? 
         // loop-invariant keeps 2*CPT fp64 values out of the register file
         int cgz = cg;
         asm volatile("" : "+v"(cgz));
-        if constexpr (TILED && DEFL) {
+        if constexpr (TILED && DEFL && STORE) {
             // pacing: `rdst` x 64 cycles of s_sleep before a tile's loads go out (launcher)
             if (!LATE_FILL || !first_tile)  // (nothing is in flight before the first tile)
                 for (int q = 0; q < pace; ++q) __builtin_amdgcn_s_sleep(1);
@@ -578,7 +583,9 @@ __global__ __launch_bounds__(NT, (NT / 256) * ((CPT <= 16 && !DEFL && !ONEWG) ? 
                 const double pk = ps[cgz + CG * j];
 #pragma unroll
                 for (int e = 0; e < V; ++e) x[j].v[e] = (T)fma(tp[e], pk, (double)x[j].v[e]);
-                if constexpr (TILED) {
+                if constexpr (!STORE) {
+                    continue;  // the deflated tile lives in registers only
+                } else if constexpr (TILED) {
                     const __amdgpu_buffer_rsrc_t rd =
                         __builtin_amdgcn_make_buffer_rsrc(dst + tile * tsd, (short)0, trec, BUF_WORD3);
                     // (write-through stores -- sc1 | nt, sc0 | sc1 | nt: nothing dirty in L2 when the launch ends -- measured in
@@ -599,7 +606,7 @@ __global__ __launch_bounds__(NT, (NT / 256) * ((CPT <= 16 && !DEFL && !ONEWG) ? 
         }
         // the deflated tile goes out BEFORE the score arithmetic (left to itself the compiler sinks the stores behind the
         // score FMAs and the first butterfly level: 1.387 instead of 1.354 ms per launch at config 3)
-        if constexpr (DEFL) __builtin_amdgcn_sched_barrier(0);
+        if constexpr (DEFL && STORE) __builtin_amdgcn_sched_barrier(0);
         // score: partial over this lane's columns, then over the lanes / waves sharing the rows
         double tp2[V];
 #pragma unroll
@@ -808,6 +815,7 @@ __global__ __launch_bounds__(NT, (NT / 256) * 2) void deflate_score_kernel(
 // costs the hot loops nothing.  Element (i, k) of src / dst is at (i / rs) * ts + i % rs + k * ld (column-major: ts = rs).
 // Steps, each optional:  x -= tprev[i] * pprev[k]  ->  dst  ;  t[i] = sum_k x v[k] -> tout (or t = tgiven[i])  ;
 // part[k] = sum_i x t[i]  (or, with Y: part[k + m K] = sum_i x Y[i, m])  ;  *sspart = sum_i t[i]^2.
+// dst == nullptr with tprev set (the last deflating pass of a fit): the rows are deflated and used, not stored.
 // ---------------------------------------------------------------------------------------------------------------------
 template <typename T>
 struct TailArgs {
@@ -855,7 +863,7 @@ __global__ __launch_bounds__(WG) void tail_rows_kernel(TailArgs<T> a) {
             T *drow = a.dst + (i / a.rd) * a.tsd + i % a.rd;
             for (int k = threadIdx.x; k < a.K; k += WG) drow[(i64)k * a.ldd] = (T)0;
         }
-    if (a.part) {  // (every thread re-reads the elements it wrote itself)
+    if (a.part) {  // (every thread re-reads the elements it wrote itself; without dst it deflates them again: the same bits)
         const int nm = a.Y ? a.M : 1;
         for (int k = threadIdx.x; k < a.K; k += WG)
             for (int m = 0; m < nm; ++m) {
@@ -863,8 +871,13 @@ __global__ __launch_bounds__(WG) void tail_rows_kernel(TailArgs<T> a) {
                 for (int r = 0; r < MAXR; ++r)
                     if (r < a.nrows) {
                         const i64 i = a.row0 + r;
-                        const double x = a.dst ? (double)a.dst[(i / a.rd) * a.tsd + i % a.rd + (i64)k * a.ldd]
-                                               : (double)a.src[(i / a.rs) * a.tss + i % a.rs + (i64)k * a.lds];
+                        double x;
+                        if (a.dst) {
+                            x = (double)a.dst[(i / a.rd) * a.tsd + i % a.rd + (i64)k * a.ldd];
+                        } else {
+                            const T xs = a.src[(i / a.rs) * a.tss + i % a.rs + (i64)k * a.lds];
+                            x = a.tprev ? (double)(T)fma(-(double)a.tprev[i], a.pprev[k], (double)xs) : (double)xs;
+                        }
                         p = fma(x, a.Y ? (double)a.Y[i + (i64)m * a.ldy] : t[r], p);
                     }
                 a.part[k + (i64)m * a.K] = p;
@@ -1372,12 +1385,14 @@ bool fused_pass_covers(const T *X, i64 ldx, i64 N, int K, const T *Tm, i64 ldt) 
 // rc: 0 = launched, 1 = shape/alignment not covered (caller falls back to the one-product
 // kernels), <0 = launch error.  grid_hint: 0 = auto.  (ldx, tsx) / (ldd, tsd): column and tile strides.
 // rdst > 0 (with CGX = 32 and a deflating pass): the destination uses tiles of rdst rows.
+// store = false (with a deflating pass): deflate in registers only -- nothing is written to dst, which is neither checked nor
+// touched (rdst must be 0); grid, walk and weights stay those of the storing pass: the same sums bit for bit.
 template <typename T, int CGX = 32>
 int launch_fused_pass(hipStream_t stream, int num_cu, const T *X, i64 ldx, i64 tsx, T *dst, i64 ldd, i64 tsd,
                       i64 N, int K, const double *v, const T *tprev, const double *pprev, T *tout,
                       double *part, int max_rows, double *sspart, int *nb, int *nss, int grid_hint, int rdst = 0,
                       bool src_padded = false, const SliceTail *tail = nullptr, bool *tail_used = nullptr,
-                      bool *upd_done = nullptr) {
+                      bool *upd_done = nullptr, bool store = true) {
     // *upd_done: the tail ran the component update as well (tail->upd set by the caller and the shape has room for it)
     // tail (cnt, red, npush, seq, peers set by the caller): sum the partial rows inside the launch (slice_tail) when the
     // grid is large enough; *tail_used tells the caller whether reduce_partials_kernel is still to run
@@ -1388,16 +1403,18 @@ int launch_fused_pass(hipStream_t stream, int num_cu, const T *X, i64 ldx, i64 t
     constexpr int CG = NT / (R / V);
     static_assert(CG == CGX, "tile shape");
     const bool defl = (tprev != nullptr);
-    if (!elem_aligned<T>(tout) || (defl && (!cols_aligned<T>(dst, ldd) || !elem_aligned<T>(tprev)))) return 1;
+    const bool stores = defl && store;  // the pass has a store side
+    if (!stores) dst = nullptr;
+    if (!elem_aligned<T>(tout) || (defl && !elem_aligned<T>(tprev)) || (stores && !cols_aligned<T>(dst, ldd))) return 1;
     // the byte span of the column groups behind one descriptor (its num_records, and every lane offset) must stay below
     // 2^31: all CG groups of the workgroup, or -- EDGE -- the WAVE / RP groups of one wave
     int edge = edge_level<T>(X, ldx, CG, WAVE / (R / V));
-    if (edge < 0 || (edge == 0 && tsx % V != 0) || (defl && tsd % V != 0)) return 1;
+    if (edge < 0 || (edge == 0 && tsx % V != 0) || (stores && tsd % V != 0)) return 1;
     // (512 groups: 32 columns per lane only for read-only passes -- v alone is 128 KB of LDS there, p_prev would not fit)
     if (K > CG * ((CGX == 64 || CGX == 128 || CGX == 256 || CGX < 32 || (CGX == 512 && defl)) ? 16 : 32) || N < 1 || max_rows < 2) return 1;
     if ((N + V) * (i64)sizeof(T) >= (1ll << 31)) return 1;  // one descriptor per score column
-    if (defl && (i64)CG * ldd * (i64)sizeof(T) >= (1ll << 31)) return 1;
-    if (rdst > 0 && (CGX != 32 || !defl || rdst < V || R % rdst != 0 ||
+    if (stores && (i64)CG * ldd * (i64)sizeof(T) >= (1ll << 31)) return 1;
+    if (rdst > 0 && (CGX != 32 || !stores || rdst < V || R % rdst != 0 ||
                      ((i64)(R / rdst) * tsd + (i64)CG * ldd) * (i64)sizeof(T) >= (1ll << 31)))
         return 1;
     if (CGX > 32 && edge != 0) return 1;  // (the short tiles only ever hold the library's own copy)
@@ -1443,7 +1460,7 @@ int launch_fused_pass(hipStream_t stream, int num_cu, const T *X, i64 ldx, i64 t
             TailArgs<T> a;
             a.src = X; a.lds = ldx; a.tss = tsx; a.rs = R;
             if (defl) {
-                a.dst = dst; a.ldd = ldd; a.tsd = tsd; a.rd = rdst > 0 ? rdst : R;
+                if (stores) { a.dst = dst; a.ldd = ldd; a.tsd = tsd; a.rd = rdst > 0 ? rdst : R; }
                 a.tprev = tprev; a.pprev = pprev;
             }
             a.v = v; a.tout = tout; a.part = part + grid * K; a.sspart = sspart + grid;
@@ -1457,7 +1474,8 @@ int launch_fused_pass(hipStream_t stream, int num_cu, const T *X, i64 ldx, i64 t
         // per CU beats two); throttled a little further it gains another 1.5-3 % on every shape measured -- config 3
         // 0.752 -> 0.772 / 0.774 -> 0.787 of peak on two boxes, an eighth of it 0.723 -> 0.736, config 4 0.784 -> 0.799, a
         // shard of config 5 0.773 -> 0.786 -- while 64 x 64 cycles already cost one box 2 % (profiles/r4/pace_sweep_*.txt).
-        const bool tiled = defl && edge == 0 && rdst == 0 && ldx == R && ldd == R && tsx == (i64)R * K && tsd == (i64)R * K;
+        // (a pass that does not store: decided from the source alone)
+        const bool tiled = defl && edge == 0 && rdst == 0 && ldx == R && tsx == (i64)R * K && (!stores || (ldd == R && tsd == (i64)R * K));
         // Shares of the tiles by XCD class (kernel comment, "weighted walk"): read+write sweeps at one workgroup per CU -- the
         // odd XCDs take rho times as long per tile (measured 1.05-1.10 over configs 3, 4, 5: profiles/r5/pass_stamps_shapes.txt)
         // (bit 16 of the pacing word: the operand vectors go to LDS behind the first tile's loads -- 191.5 -> 190.0 us per component
@@ -1481,7 +1499,7 @@ int launch_fused_pass(hipStream_t stream, int num_cu, const T *X, i64 ldx, i64 t
         // (the one-descriptor form for READ-ONLY passes over the copy was built in round 5: 52 bytes of scratch per lane instead
         // of 24 -- the 128-register shape's spills are its 64 tile + 32 accumulator registers, not its descriptors)
         if (CGX > 32 && defl && !tiled) return 1;
-#define FUSED_LAUNCH(CPT_, DEFL_, EDGE_, TILED_, dyn_)                                                                    \
+#define FUSED_LAUNCH(CPT_, DEFL_, EDGE_, TILED_, STORE_, dyn_)                                                            \
     do {                                                                                                                  \
         if constexpr (!(DEFL_) && (CPT_) <= 16 && CGX <= 64 && (EDGE_) == 0) {                                            \
             if (onewg) {                                                                                                  \
@@ -1490,26 +1508,27 @@ int launch_fused_pass(hipStream_t stream, int num_cu, const T *X, i64 ldx, i64 t
                 break;                                                                                                    \
             }                                                                                                             \
         }                                                                                                                 \
-        auto kfn = &fused_pass_kernel<T, V, R, NT, CPT_, DEFL_, AUX_NT, AUX_NT, false, EDGE_, TILED_>;                   \
+        auto kfn = &fused_pass_kernel<T, V, R, NT, CPT_, DEFL_, AUX_NT, AUX_NT, false, EDGE_, TILED_, false, STORE_>;    \
         if ((dyn_) > 48 * 1024 && !raise_dynamic_lds(reinterpret_cast<const void *>(kfn), (int)(dyn_))) return 1;         \
-        hipLaunchKernelGGL(kfn, g, b, dyn_, stream, X, ldx, tsx, dst, ldd, tsd, Nf, K, v, tprev, pprev, tout, part, sspart, (TILED_) ? (2 * (CPT_)) | 0x10000 : 0, N, st, wk); \
+        hipLaunchKernelGGL(kfn, g, b, dyn_, stream, X, ldx, tsx, dst, ldd, tsd, Nf, K, v, tprev, pprev, tout, part, sspart, (TILED_) ? ((STORE_) ? 2 * (CPT_) : 0) | 0x10000 : 0, N, st, wk); \
     } while (0)
-#define FUSED_EDGE(CPT_, DEFL_, dyn_)                                                                                     \
+#define FUSED_EDGE(CPT_, DEFL_, STORE_, dyn_)                                                                             \
     do {                                                                                                                  \
         if constexpr (DEFL_) {                                                                                            \
-            if (tiled) { FUSED_LAUNCH(CPT_, DEFL_, 0, true, dyn_); break; }                                               \
+            if (tiled) { FUSED_LAUNCH(CPT_, DEFL_, 0, true, STORE_, dyn_); break; }                                       \
         }                                                                                                                 \
         if constexpr (CGX <= 32) {                                                                                        \
-            if (edge == 2) { FUSED_LAUNCH(CPT_, DEFL_, 2, false, dyn_); break; }                                          \
-            if (edge == 1) { FUSED_LAUNCH(CPT_, DEFL_, 1, false, dyn_); break; }                                          \
+            if (edge == 2) { FUSED_LAUNCH(CPT_, DEFL_, 2, false, STORE_, dyn_); break; }                                  \
+            if (edge == 1) { FUSED_LAUNCH(CPT_, DEFL_, 1, false, STORE_, dyn_); break; }                                  \
         }                                                                                                                 \
-        if constexpr (CGX <= 32 || !DEFL_) FUSED_LAUNCH(CPT_, DEFL_, 0, false, dyn_);                                     \
+        if constexpr (CGX <= 32 || !DEFL_) FUSED_LAUNCH(CPT_, DEFL_, 0, false, STORE_, dyn_);                             \
     } while (0)
 #define FUSED_CASE(CPT_)                                                                                                  \
     do {                                                                                                                  \
         const size_t dyn = ((size_t)2 * CG * CPT_ * sizeof(double) > 48 * 1024) ? (size_t)2 * CG * CPT_ * sizeof(double) : 0; \
-        if (defl) FUSED_EDGE(CPT_, true, dyn);                                                                            \
-        else FUSED_EDGE(CPT_, false, (CGX >= 512 ? dyn / 2 : dyn));   /* (no p_prev: the second half is never touched) */ \
+        if (stores) FUSED_EDGE(CPT_, true, true, dyn);                                                                    \
+        else if (defl) FUSED_EDGE(CPT_, true, false, dyn);            /* (the last deflating pass of a fit) */            \
+        else FUSED_EDGE(CPT_, false, true, (CGX >= 512 ? dyn / 2 : dyn));   /* (no p_prev: the second half is never touched) */ \
     } while (0)
         if constexpr (CGX == 32) {
             if (rdst > 0) {  // first deflation into shorter tiles: only the 32-columns-per-lane shape needs it
@@ -1539,7 +1558,7 @@ int launch_fused_pass(hipStream_t stream, int num_cu, const T *X, i64 ldx, i64 t
             // at 16 columns per lane; read-only passes up to K = 16384 at 32 (256 VGPRs, one workgroup per CU)
             if (K <= CG * 12) FUSED_CASE(12);
             else if (K <= CG * 16) FUSED_CASE(16);
-            else FUSED_EDGE(32, false, (size_t)CG * 32 * sizeof(double));
+            else FUSED_EDGE(32, false, true, (size_t)CG * 32 * sizeof(double));
         } else {
             if (K <= CG * 12) FUSED_CASE(12);
             else FUSED_CASE(16);  // 256 column groups x 2 row lanes: K <= 4096 at 16 columns per lane
@@ -1553,7 +1572,7 @@ int launch_fused_pass(hipStream_t stream, int num_cu, const T *X, i64 ldx, i64 t
             TailArgs<T> a;
             a.src = X; a.lds = ldx; a.tss = tsx; a.rs = R;
             if (defl) {
-                a.dst = dst; a.ldd = ldd; a.tsd = tsd; a.rd = rdst > 0 ? rdst : R;
+                if (stores) { a.dst = dst; a.ldd = ldd; a.tsd = tsd; a.rd = rdst > 0 ? rdst : R; }
                 a.tprev = tprev; a.pprev = pprev;
             }
             a.v = v; a.tout = tout; a.part = part + grid * K; a.sspart = sspart + grid;

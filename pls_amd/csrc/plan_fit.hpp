@@ -525,6 +525,11 @@ int fit_device(pls_hip_context *c, const T *X, i64 ldx, const T *Y, i64 ldy, i64
         // over the device-side exchange the tail pushes, waits for the peers' pushes and updates (other reducers: a call
         // between the pass and the update, so the update stays a launch of its own)
         const bool defl_pass = nipals && a > 0;
+        // The last deflating pass of a fit stores nothing: X_{A-1} is read by no later launch, and the work buffer is scratch,
+        // not an output (after a fit it holds X_{A-2}).  On the three fused routes below.  Not on the semi-fused route (the
+        // loading launch behind launch_deflate_score reads what that stored: the store is not dead), not on the unfused plan;
+        // the deferred plan has always skipped its last store.
+        const bool store_x = (a + 1 < A);  // X_a goes back to memory (false: it lives in the pass's registers only)
         const bool want_upd = tail.cnt && (c->env.tail_update == 2 || (c->env.tail_update == 1 && !defl_pass)) && M == 1 &&
                               K <= plsk::UPD1_KMAX && update_is_single(K, M, A, a) && (!c->reducer || want_push);
         tail.npush = 0;
@@ -584,17 +589,17 @@ int fit_device(pls_hip_context *c, const T *X, i64 ldx, const T *Y, i64 ldy, i64
                 const double *pprev = (nipals && a > 0) ? P + (i64)(a - 1) * K : nullptr;
                 int rc;
                 {
-                    const i64 bytes = (tprev ? 2 : 1) * (i64)N * K * sizeof(T) +
+                    const i64 bytes = ((tprev && store_x) ? 2 : 1) * (i64)N * K * sizeof(T) +
                                       (tprev ? 2 : 1) * (i64)N * sizeof(T) + (tprev ? 3 : 2) * (i64)K * 8;
                     Scope s(c, PLS_HIP_FAM_FUSED, bytes);
                     if (mid_cg && a >= 2)  // half-height tiles of the working copy, in place
                         rc = plsk::launch_fused_pass<T, 64>(c->stream, c->num_cu, work, ldw, tsw, work, ldw, tsw, N, K, v,
                                                             tprev, pprev, Tm + (i64)a * ldt, part, (int)prow, sspart,
-                                                            &nb, &nss, (int)c->opt_fused_grid, 0, true, &tail, &tail_used, &upd_done);
-                    else {  // (a == 1 with mid_cg: X in 256-byte segments -> half-height tiles)
-#define TALL_PASS(CG_) plsk::launch_fused_pass<T, CG_>(c->stream, c->num_cu, Xc, ldc, tsc, tprev ? work : nullptr, ldw, tsw, N, K, v, tprev, \
+                                                            &nb, &nss, (int)c->opt_fused_grid, 0, true, &tail, &tail_used, &upd_done, store_x);
+                    else {  // (a == 1 with mid_cg: X in 256-byte segments -> half-height tiles; A = 2: nothing is stored, no tile shape)
+#define TALL_PASS(CG_) plsk::launch_fused_pass<T, CG_>(c->stream, c->num_cu, Xc, ldc, tsc, (tprev && store_x) ? work : nullptr, ldw, tsw, N, K, v, tprev, \
                                                        pprev, Tm + (i64)a * ldt, part, (int)prow, sspart, &nb, &nss,                        \
-                                                       (int)c->opt_fused_grid, (mid_cg && tprev) ? (int)WR : 0, Xc == work, &tail, &tail_used, &upd_done)
+                                                       (int)c->opt_fused_grid, (mid_cg && tprev && store_x) ? (int)WR : 0, Xc == work, &tail, &tail_used, &upd_done, store_x)
                         rc = tall_cg == 8 ? TALL_PASS(8) : (tall_cg == 16 ? TALL_PASS(16) : TALL_PASS(32));
 #undef TALL_PASS
                     }
@@ -603,7 +608,7 @@ int fit_device(pls_hip_context *c, const T *X, i64 ldx, const T *Y, i64 ldy, i64
                 if (rc == 0) {
                     LAUNCH_CHECK(c);
                     done = true;
-                    if (tprev) { Xc = work; ldc = ldw; tsc = tsw; cur_tiled = tiled_work; }
+                    if (tprev && store_x) { Xc = work; ldc = ldw; tsc = tsw; cur_tiled = tiled_work; }
                     if (!tail_used) CHK(launch_reduce(c, part, nb, K, sspart, nss, red));
                 } else {
                     return fail(c, PLS_HIP_ERR_DEVICE, "fused pass launch failed");
@@ -622,11 +627,11 @@ int fit_device(pls_hip_context *c, const T *X, i64 ldx, const T *Y, i64 ldy, i64
                     LAUNCH_CHECK(c);
                 }
                 {
-                    const i64 bytes = (tprev ? 2 : 1) * ((i64)N * K * sizeof(T) + (i64)N * sizeof(T)) + 3 * (i64)K * 8;
+                    const i64 bytes = ((tprev && store_x) ? 2 : 1) * (i64)N * K * sizeof(T) + (tprev ? 2 : 1) * (i64)N * sizeof(T) + 3 * (i64)K * 8;
                     Scope s(c, PLS_HIP_FAM_FUSED, bytes);
 #define WIDE_PASS(CG_) plsk::launch_fused_pass<T, CG_>(c->stream, c->num_cu, work, ldw, tsw, work, ldw, tsw, N, K, v, tprev, pprev, \
                                                         Tm + (i64)a * ldt, part, (int)prow, sspart, &nb, &nss, (int)c->opt_fused_grid, 0, true, \
-                                                        &tail, &tail_used, &upd_done)
+                                                        &tail, &tail_used, &upd_done, store_x)
                     rc = wide_cg == 8 ? WIDE_PASS(8) : (wide_cg == 16 ? WIDE_PASS(16) : (wide_cg == 32 ? WIDE_PASS(32)
                          : (wide_cg == 64 ? WIDE_PASS(64) : (wide_cg == 128 ? WIDE_PASS(128) : (wide_cg == 256 ? WIDE_PASS(256) : WIDE_PASS(512))))));
 #undef WIDE_PASS
