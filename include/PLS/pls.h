@@ -57,12 +57,22 @@ namespace PLS {
 typedef std::vector<Mat2D> ResidualData;
 class Model;
 
+struct ValidationSummary;  // defined in pls.cpp
+
 class Residual {
     const std::vector<Mat2D> _residual;
     const std::string _method_label;
+    // What validation() and optimal_num_components() report, formed on the device when the residuals were produced
+    // (pls_hip_validation in pls_hip.h): PRESS per (response, component count), the column of its minimum and the
+    // Wilcoxon p-value of every smaller component count against it.  Null (a Residual without it): the host loops run.
+    const std::shared_ptr<const ValidationSummary> _summary;
     Residual(const std::vector<Mat2D> &residual, const std::string &method)
         : _residual(residual), _method_label(method) {}
+    Residual(const std::vector<Mat2D> &residual, const std::string &method,
+             const std::shared_ptr<const ValidationSummary> &summary)
+        : _residual(residual), _method_label(method), _summary(summary) {}
     friend class Model;
+    friend struct ValidationSummary;
 
 public:
     const std::vector<Mat2D> errors() const { return _residual; }

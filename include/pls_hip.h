@@ -100,10 +100,15 @@ typedef enum {
     PLS_HIP_OPT_DEFER = 7,       /* NIPALS plan, K <= 512: write the deflated matrix back every D-th component only (1..4); the
                                     D - 1 pending rank-1 updates are re-applied in registers.  1 (default) = explicit deflation:
                                     every X_a that a later pass reads is materialised (the last one, which none reads, is not) */
-    PLS_HIP_OPT_GRAPH = 8        /* 1: a device-memory pls_hip_fit that repeats an earlier call (same pointers, shapes, options) is
+    PLS_HIP_OPT_GRAPH = 8,       /* 1: a device-memory pls_hip_fit that repeats an earlier call (same pointers, shapes, options) is
                                     captured into a hipGraph on its second occurrence and replayed as ONE graph launch from the
                                     third on.  Single rank, profiling off, a stream of its own (not the default stream).  0 (default): every
                                     call enqueues its kernels */
+    PLS_HIP_OPT_VALIDATION_LDS_ROWS = 9 /* pls_hip_validation: the largest nobs whose signed-rank sums are formed by ONE workgroup per
+                                    (response, alternative) pair, the column pair sorted in LDS; longer columns take the streaming
+                                    radix sort.  Default (what pls_hip_get_option returns on a fresh handle): the most this device
+                                    allows (16000 rows with 160 KiB of LDS per workgroup).  May be lowered, 0 = every column streams;
+                                    a value above the device's own is PLS_HIP_ERR_INVALID */
 } pls_hip_option;
 
 /*
@@ -267,6 +272,38 @@ PLS_HIP_API int pls_hip_model_sse(pls_hip_handle h, const void *X, int64_t ldx, 
 PLS_HIP_API int pls_hip_cv_folds(pls_hip_handle h, const void *X, int64_t ldx, const void *Y, int64_t ldy,
                                  int64_t N, int64_t K, int64_t M, int64_t A, const int64_t *test_idx,
                                  int64_t test_size, int64_t num_folds, int dtype, int mem, double *E);
+
+/*
+ * Validation summary of cross-validation residuals E (the layout pls_hip_cv_folds writes: M matrices of nobs x A, column
+ * (m, c) at E + (m*A + c)*nobs; fp64; host or device memory, the outputs live where E lives).  Model::validation and
+ * optimal_num_components (src/pls.cpp:235-289) without the host loops:
+ *   PRESS (M x A, ld M)   PRESS[m + c*M] = sum_i E[m][i, c]^2.  Fixed summation order: two calls on the same E return the same
+ *                         bits (a column is summed in runs of 4096 rows, the runs in index order).
+ *   ref (M, int64)        0-based first column with the strictly smallest PRESS of the response (scan from column 0 with `<`: a
+ *                         NaN PRESS never replaces the current minimum, a NaN in column 0 is never replaced).
+ *   D (M x A, ld M)       for alt < ref[m]: the Wilcoxon signed-rank sum of del_i = |E[m][i, ref]| - |E[m][i, alt]|,
+ *                         D = sum_i rank_i * sign(del_i), rank_i = 1-based position of |del_i| in ascending order; exact (it is
+ *                         accumulated in 64-bit integers).  Entries with alt >= ref[m] are 0.
+ *                         TIES in |del| rank in ROW ORDER (a stable sort).  The reference sorts with std::sort (src/pls.cpp:198),
+ *                         which leaves the order of equal keys unspecified; this library defines it.  Rows with del == 0 or NaN
+ *                         have sign 0; NaNs rank last.
+ *   probw (M x A, ld M)   for alt < ref[m]: 1 - normalcdf((v - ev) / sv) with t = n(n+1)/2, v = (t - D)/2, ev = t/2,
+ *                         sv = sqrt(n(n+1)(2n+1)/24) (src/pls.cpp:204-210; n(n+1)(2n+1) is formed in fp64 -- the reference's
+ *                         size_t product wraps beyond n = 2.09e6).  Entries with alt >= ref[m] are NaN.
+ * EVERY alt < ref[m] is evaluated (the reference stops at the first alt with probw > ALPHA, :281-286), so the result does not
+ * depend on ALPHA; the pick is 1 + the first alt < ref[m] with probw > ALPHA, else ref[m] + 1.
+ * Any of PRESS / D / probw / ref may be NULL.  nobs, A, M >= 1 and E non-NULL, else PLS_HIP_ERR_INVALID.
+ * mem == DEVICE: the work is enqueued on the handle's stream, nothing returns to the host.  mem == HOST: E crosses through the
+ * pinned staging pipeline -- in pieces of at most 64 MB through one buffer when neither D nor probw is asked for, as a whole
+ * otherwise -- and the call returns with the results in place.
+ * Columns of at most PLS_HIP_OPT_VALIDATION_LDS_ROWS rows: one launch for all pairs, one workgroup sorting each pair in LDS.
+ * Longer columns: a stable least-significant-digit radix sort of the 63 magnitude bits (8 passes of 8 bits, the sign rides in
+ * bit 63) in library workspace, the pairs batched per round as far as 4 GB (2 * nobs * 8 bytes and nobs / 2 bytes of counters per
+ * pair) and the device's free memory allow.
+ * On a handle with a reducer installed the call is LOCAL: no message is sent (every rank holds the same E).
+ */
+PLS_HIP_API int pls_hip_validation(pls_hip_handle h, const double *E, int64_t nobs, int64_t A, int64_t M, int mem,
+                                   double *PRESS, double *D, double *probw, int64_t *ref);
 
 /* ---- synthetic inputs, generated on the device (DESIGN.md "Synthetic inputs") ------ */
 

@@ -21,6 +21,7 @@ F64, F32 = 0, 1
 MEM_HOST, MEM_DEVICE = 0, 1
 ALGO_KERNEL, ALGO_NIPALS, ALGO_GRAM, ALGO_AUTO = 0, 1, 2, 3
 OPT_ALGO, OPT_FUSE, OPT_PROFILE, OPT_POWER_ITERS, OPT_FUSED_GRID, OPT_WORK_LAYOUT, OPT_DEFER, OPT_GRAPH = 1, 2, 3, 4, 5, 6, 7, 8
+OPT_VALIDATION_LDS_ROWS = 9
 REDUCE_SLICES = 8
 XCHG_HANDLE_BYTES = 160  # PLS_HIP_XCHG_HANDLE_BYTES
 FAM_XTY, FAM_XB, FAM_DEFLATE, FAM_FUSED, FAM_SMALL, FAM_COUNT = 0, 1, 2, 3, 4, 5
@@ -72,6 +73,7 @@ PROTOTYPES = [
     ("pls_hip_sse_by_components", _int, [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _int, _vp]),
     ("pls_hip_model_sse", _int, [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _int, _int, _vp]),
     ("pls_hip_cv_folds", _int, [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _int, _int, _vp]),
+    ("pls_hip_validation", _int, [_vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp]),
     ("pls_hip_synth_x", _int, [_vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_uint64, _int]),
     ("pls_hip_synth_y", _int, [_vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_uint64, _int]),
     # one process, several GPUs: groups and resident matrices

@@ -31,6 +31,9 @@ struct pls_hip_context {
     std::vector<uint64_t> graph_key, graph_seen;
     hipGraphExec_t graph_exec = nullptr;
     DevBuf zeros, part, sspart, xbpart, wide1, red, red2, xx, xyp, praw, xy, v, cs, coop, lm, gxx, gxy, tab, work, cvidx, cvx, cvy, cvws, cve, cvtx, cvty, cvtt, cvm, cvkeep, cvred, hX, hY, hT, hW, hP, hQ, hR, hB, hIn, hOut;
+    DevBuf valout, valpart, vale, valacc, valkeys, valhist;  // pls_hip_validation (plan_validation.hpp)
+    i64 opt_val_lds_rows = -1;  // PLS_HIP_OPT_VALIDATION_LDS_ROWS; -1 = the device's own limit
+    i64 val_lds_rows_dev = -1;  // that limit, found on first use
     std::string err;
     // profiling
     std::vector<hipEvent_t> ev_pool;  // grows until pls_hip_get_timing harvests and recycles it

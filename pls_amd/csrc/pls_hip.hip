@@ -31,6 +31,7 @@
 #include "xb_mfma4w.hpp"
 #include "syrk_kernels.hpp"
 #include "cv_kernels.hpp"
+#include "validation_kernels.hpp"
 #include "synth_kernels.hpp"
 #include "host_pipeline.hpp"
 #include "exchange_kernels.hpp"
@@ -43,6 +44,7 @@ using plsk::i64;
 #include "plan_common.hpp"
 #include "plan_fit.hpp"
 #include "host_entry.hpp"
+#include "plan_validation.hpp"
 
 // =============================================================================================
 // C-ABI
@@ -102,7 +104,8 @@ int pls_hip_destroy(pls_hip_handle h) {
     (void)hipStreamSynchronize(h->stream);
     DevBuf *bufs[] = {&h->tailcnt, &h->resident, &h->rgflags, &h->zeros, &h->part, &h->sspart, &h->xbpart, &h->wide1, &h->red, &h->red2, &h->xx, &h->xyp, &h->praw, &h->xy, &h->v, &h->cs, &h->coop, &h->lm, &h->gxx, &h->gxy, &h->tab,
                       &h->cvidx, &h->cvx, &h->cvy, &h->cvws, &h->cve, &h->cvtx, &h->cvty, &h->cvtt, &h->cvm, &h->cvkeep, &h->cvred, &h->work, &h->hX, &h->hY,
-                      &h->hT, &h->hW, &h->hP, &h->hQ, &h->hR, &h->hB, &h->hIn, &h->hOut};
+                      &h->hT, &h->hW, &h->hP, &h->hQ, &h->hR, &h->hB, &h->hIn, &h->hOut, &h->valout, &h->valpart, &h->vale, &h->valacc, &h->valkeys,
+                      &h->valhist};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (void *q : h->graveyard) (void)hipFree(q);
@@ -150,6 +153,10 @@ int pls_hip_set_option(pls_hip_handle h, int option, int64_t value) {
             h->opt_defer = value;
             return PLS_HIP_OK;
         case PLS_HIP_OPT_GRAPH: h->opt_graph = value ? 1 : 0; return PLS_HIP_OK;
+        case PLS_HIP_OPT_VALIDATION_LDS_ROWS:
+            if (value < 0 || value > val_lds_rows_device(h)) return fail(h, PLS_HIP_ERR_INVALID, "validation LDS rows out of range");
+            h->opt_val_lds_rows = value;
+            return PLS_HIP_OK;
         default: return fail(h, PLS_HIP_ERR_INVALID, "unknown option");
     }
 }
@@ -166,6 +173,7 @@ int pls_hip_get_option(pls_hip_handle h, int option, int64_t *value) {
         case PLS_HIP_OPT_GRAPH: *value = h->opt_graph; return PLS_HIP_OK;
         case PLS_HIP_OPT_WORK_LAYOUT: *value = h->opt_work_layout; return PLS_HIP_OK;
         case PLS_HIP_OPT_DEFER: *value = h->opt_defer; return PLS_HIP_OK;
+        case PLS_HIP_OPT_VALIDATION_LDS_ROWS: *value = h->opt_val_lds_rows >= 0 ? h->opt_val_lds_rows : val_lds_rows_device(h); return PLS_HIP_OK;
         default: return fail(h, PLS_HIP_ERR_INVALID, "unknown option");
     }
 }
@@ -627,6 +635,19 @@ int pls_hip_model_sse(pls_hip_handle h, const void *X, int64_t ldx, const void *
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     return PLS_HIP_OK;
+}
+
+int pls_hip_validation(pls_hip_handle h, const double *E, int64_t nobs, int64_t A, int64_t M, int mem, double *PRESS, double *D,
+                       double *probw, int64_t *ref) {
+    CHK(check_handle(h));
+    if (mem != PLS_HIP_MEM_HOST && mem != PLS_HIP_MEM_DEVICE) return fail(h, PLS_HIP_ERR_INVALID, "bad mem kind");
+    if (!E || nobs < 1 || A < 1 || M < 1) return fail(h, PLS_HIP_ERR_INVALID, "bad validation arguments");
+    if (nobs > ((i64)1 << 31) - 1 || A > (1 << 20) || M > (1 << 20) || M * A > (1 << 24) ||
+        ((nobs + plsk::VAL_CH - 1) / plsk::VAL_CH) * M * A > ((i64)1 << 31) - 1)
+        return fail(h, PLS_HIP_ERR_UNSUPPORTED, "validation: nobs < 2^31, M A <= 2^24, M A ceil(nobs / 4096) < 2^31");
+    CHK(set_device(h));
+    // (local on a row-sharded handle: every rank holds the same E, nothing is exchanged)
+    return validation_impl(h, E, nobs, (int)A, (int)M, mem, PRESS, D, probw, ref);
 }
 
 int pls_hip_synth_x(pls_hip_handle h, void *X, int64_t ldx, int64_t row0, int64_t nrows, int64_t K,

@@ -216,6 +216,43 @@ struct PLS::Model::Resident {
     explicit Resident(const Ctx &c) : X(c), Y(c), T(c) {}
 };
 
+// The validation summary a Residual carries (include/PLS/pls.h): outputs of pls_hip_validation, M x A with ld M.
+struct PLS::ValidationSummary {
+    Index M = 0, A = 0, nobs = 0;
+    std::vector<float_type> press, probw;
+    std::vector<int64_t> ref;  // 0-based column of the PRESS minimum per response
+    static const ValidationSummary *of(const Residual &r) { return r._summary.get(); }
+};
+
+namespace {
+
+// e: residuals in the layout of pls_hip_cv_folds, HOST memory (M matrices of nobs x A).  One more trip of E to the device
+// (INTEGRATION.md); h: the handle of a device of the context, the caller holds the context's lock.
+std::shared_ptr<const PLS::ValidationSummary> summarise(pls_hip_handle h, const std::vector<float_type> &e, Index nobs, Index A,
+                                                        Index M) {
+    std::shared_ptr<PLS::ValidationSummary> s = std::make_shared<PLS::ValidationSummary>();
+    s->M = M; s->A = A; s->nobs = nobs;
+    s->press.resize(static_cast<size_t>(M * A));
+    s->probw.resize(static_cast<size_t>(M * A));
+    s->ref.resize(static_cast<size_t>(M));
+    if (pls_hip_validation(h, e.data(), nobs, A, M, PLS_HIP_MEM_HOST, s->press.data(), nullptr, s->probw.data(), s->ref.data()) !=
+        PLS_HIP_OK)
+        throw std::runtime_error(std::string("PLS: pls_hip_validation failed: ") + pls_hip_last_error(h));
+    return s;
+}
+
+// the flat residuals -> Residual::errors()
+std::vector<Mat2D> unpack_residuals(const std::vector<float_type> &e, Index nobs, Index A, Index M) {
+    std::vector<Mat2D> Ev(static_cast<size_t>(M), Mat2D::Zero(nobs, A));
+    for (Index m = 0; m < M; ++m)
+        for (Index c = 0; c < A; ++c)
+            for (Index i = 0; i < nobs; ++i)
+                Ev[static_cast<size_t>(m)](i, c) = e[static_cast<size_t>(m * nobs * A + i + c * nobs)];
+    return Ev;
+}
+
+}  // namespace
+
 namespace PLS {
 
 // Extension (no upstream counterpart): which GPUs the Models created from now on use -- {0, 1, 2, 3} = those devices, an
@@ -357,17 +394,26 @@ void rand_nchoosek(std::mt19937 &rng, std::vector<Eigen::Index> &full, std::vect
 
 // rows = Y variable, cols = number of components; RESS = sum of squared residuals, MSE = RESS/N
 Mat2D validation(const Residual &residual, const VALIDATION_OUTPUT out_type) {
-    const std::vector<Mat2D> errors = residual.errors();
-    if (errors.empty()) return Mat2D::Zero(0, 0);
-    Mat2D out = Mat2D::Zero(static_cast<Index>(errors.size()), errors[0].cols());
-    for (size_t y = 0; y < errors.size(); ++y)
-        for (Index c = 0; c < errors[y].cols(); ++c) {
-            float_type s = 0;
-            for (Index i = 0; i < errors[y].rows(); ++i) s += errors[y](i, c) * errors[y](i, c);
-            out(static_cast<Index>(y), c) = s;
-        }
+    Mat2D out;
+    float_type n = 0;
+    if (const ValidationSummary *s = ValidationSummary::of(residual)) {  // formed on the device with the residuals
+        out = Mat2D::Zero(s->M, s->A);
+        for (Index c = 0; c < s->A; ++c)
+            for (Index y = 0; y < s->M; ++y) out(y, c) = s->press[static_cast<size_t>(y + c * s->M)];
+        n = static_cast<float_type>(s->nobs);
+    } else {
+        const std::vector<Mat2D> errors = residual.errors();
+        if (errors.empty()) return Mat2D::Zero(0, 0);
+        out = Mat2D::Zero(static_cast<Index>(errors.size()), errors[0].cols());
+        for (size_t y = 0; y < errors.size(); ++y)
+            for (Index c = 0; c < errors[y].cols(); ++c) {
+                float_type s = 0;
+                for (Index i = 0; i < errors[y].rows(); ++i) s += errors[y](i, c) * errors[y](i, c);
+                out(static_cast<Index>(y), c) = s;
+            }
+        n = static_cast<float_type>(errors[0].rows());
+    }
     if (out_type == MSE) {
-        const float_type n = static_cast<float_type>(errors[0].rows());
         for (Index j = 0; j < out.cols(); ++j)
             for (Index i = 0; i < out.rows(); ++i) out(i, j) /= n;
     }
@@ -377,6 +423,21 @@ Mat2D validation(const Residual &residual, const VALIDATION_OUTPUT out_type) {
 // per Y variable: the smallest number of components whose errors are not significantly worse
 // (Wilcoxon, ALPHA) than those at the PRESS minimum (ref :265-289)
 Colsz optimal_num_components(const Residual &residual, const float_type ALPHA) {
+    if (const ValidationSummary *s = ValidationSummary::of(residual)) {
+        // every alt below the PRESS minimum was tested on the device; the first one that passes is the pick (ref :278-287)
+        Colsz best(s->M);
+        for (Index y = 0; y < s->M; ++y) {
+            const Index ref_min = static_cast<Index>(s->ref[static_cast<size_t>(y)]);
+            Index pick = ref_min;
+            for (Index alt = 0; alt < ref_min; ++alt)
+                if (s->probw[static_cast<size_t>(y + alt * s->M)] > ALPHA) {
+                    pick = alt;
+                    break;
+                }
+            best[y] = static_cast<size_t>(pick) + 1;
+        }
+        return best;
+    }
     const std::vector<Mat2D> errors = residual.errors();
     const Mat2D press = validation(residual, RESS);
     Colsz best(press.rows());
@@ -599,9 +660,11 @@ const Row Model::explained_variance(const Mat2D &X_new, const Mat2D &Y_new, cons
 // ---------------------------------------------------------------------------------------------
 namespace {
 
-// residuals of `folds` (each `test_size` held-out rows, row-major index list) -> M matrices nobs x A
+// residuals of `folds` (each `test_size` held-out rows, row-major index list) -> M matrices nobs x A, and their
+// validation summary from the device that ran the folds
 std::vector<Mat2D> run_folds(const ResidentMatrix &X, const ResidentMatrix &Y, Index N, Index K, Index M, size_t A,
-                             const std::vector<int64_t> &test_idx, size_t test_size, size_t num_folds) {
+                             const std::vector<int64_t> &test_idx, size_t test_size, size_t num_folds,
+                             std::shared_ptr<const PLS::ValidationSummary> &summary) {
     const Index nobs = static_cast<Index>(num_folds * test_size), Ai = static_cast<Index>(A);
     std::vector<float_type> e(static_cast<size_t>(nobs * Ai * M));
     {
@@ -611,6 +674,7 @@ std::vector<Mat2D> run_folds(const ResidentMatrix &X, const ResidentMatrix &Y, I
             check(ctx, pls_hip_group_cv_folds(ctx->g, X.m, Y.m, Ai, test_idx.data(), static_cast<int64_t>(test_size),
                                               static_cast<int64_t>(num_folds), e.data()),
                   "pls_hip_group_cv_folds");
+            summary = summarise(device(ctx), e, nobs, Ai, M);
         } else {  // several devices: gather the rows once, member 0's device runs the folds
             const Mat2D Xh = X.download(0, K), Yh = Y.download(0, M);
             // (a member handle carries the group's reducer; folds need none: a plain handle of the context's own)
@@ -620,14 +684,10 @@ std::vector<Mat2D> run_folds(const ResidentMatrix &X, const ResidentMatrix &Y, I
                                  static_cast<int64_t>(test_size), static_cast<int64_t>(num_folds), PLS_HIP_F64,
                                  PLS_HIP_MEM_HOST, e.data()) != PLS_HIP_OK)
                 throw std::runtime_error(std::string("PLS: pls_hip_cv_folds failed: ") + pls_hip_last_error(ctx->plain));
+            summary = summarise(ctx->plain, e, nobs, Ai, M);
         }
     }
-    std::vector<Mat2D> Ev(static_cast<size_t>(M), Mat2D::Zero(nobs, Ai));
-    for (Index m = 0; m < M; ++m)
-        for (Index c = 0; c < Ai; ++c)
-            for (Index i = 0; i < nobs; ++i)
-                Ev[static_cast<size_t>(m)](i, c) = e[static_cast<size_t>(m * nobs * Ai + i + c * nobs)];
-    return Ev;
+    return unpack_residuals(e, nobs, Ai, M);
 }
 
 }  // namespace
@@ -638,19 +698,41 @@ Residual Model::cv_LOO() const {
     if (N < 2) throw std::invalid_argument("PLS::Model::cv_LOO: need at least two observations");
     std::vector<int64_t> idx(N);
     std::iota(idx.begin(), idx.end(), int64_t(0));  // fold i leaves out row i (ref :478-488)
-    return Residual(run_folds(_data->X, _data->Y, _data->N, _data->K, _data->M, A, idx, 1, N), "LOO");
+    std::shared_ptr<const ValidationSummary> summary;
+    const std::vector<Mat2D> Ev = run_folds(_data->X, _data->Y, _data->N, _data->K, _data->M, A, idx, 1, N, summary);
+    return Residual(Ev, "LOO", summary);
 }
 
 Residual Model::cv_NEW_DATA(const Mat2D &X_new, const Mat2D &Y_new) const {
     if (X_new.cols() != R.rows() || Y_new.cols() != Q.rows())
         throw std::invalid_argument("PLS::Model::cv_NEW_DATA: column counts differ from the training data");
-    std::vector<Mat2D> Ev(static_cast<size_t>(Y_new.cols()), Mat2D::Zero(X_new.rows(), static_cast<Index>(A)));
-    for (size_t nc = 1; nc <= A; ++nc) {
-        const Mat2D res = residuals(X_new, Y_new, nc);
-        for (Index m = 0; m < res.cols(); ++m)
-            for (Index i = 0; i < res.rows(); ++i) Ev[static_cast<size_t>(m)](i, static_cast<Index>(nc - 1)) = res(i, m);
+    // The residuals for every component count follow from ONE pass S = X_new R (one upload, one product), as in
+    // print_explained_variance: Yhat_c = S[:, :c] Q[:, :c]^T, accumulated here component by component.  (The reference
+    // calls residuals() once per count, ref :500-507: A uploads and A products.)
+    const Index N = X_new.rows(), M = Y_new.cols(), Ai = static_cast<Index>(A);
+    if (X_new.rows() != Y_new.rows()) throw std::invalid_argument("PLS::Model::cv_NEW_DATA: X and Y differ in rows");
+    if (N == 0) return Residual(std::vector<Mat2D>(static_cast<size_t>(M), Mat2D::Zero(0, Ai)), "NEW DATA");
+    const Ctx ctx = _ctx ? _ctx : current_context();
+    const Mat2D S = product_on_device(ctx, X_new, real_part(R, Ai), Ai);
+    std::vector<float_type> e(static_cast<size_t>(N * Ai * M));
+    std::vector<float_type> fit(static_cast<size_t>(N));
+    for (Index m = 0; m < M; ++m) {
+        std::fill(fit.begin(), fit.end(), float_type(0));
+        for (Index c = 0; c < Ai; ++c) {
+            const float_type q = Q(m, c).real();
+            float_type *col = e.data() + static_cast<size_t>(m * N * Ai + c * N);
+            for (Index i = 0; i < N; ++i) {
+                fit[static_cast<size_t>(i)] += S(i, c) * q;
+                col[i] = Y_new(i, m) - fit[static_cast<size_t>(i)];
+            }
+        }
     }
-    return Residual(Ev, "NEW DATA");
+    std::shared_ptr<const ValidationSummary> summary;
+    {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        summary = summarise(device(ctx), e, N, Ai, M);
+    }
+    return Residual(unpack_residuals(e, N, Ai, M), "NEW DATA", summary);
 }
 
 Residual Model::cv_LSO(const float_type test_fraction, const size_t num_trials, std::mt19937 &rng) const {
@@ -669,7 +751,9 @@ Residual Model::cv_LSO(const float_type test_fraction, const size_t num_trials, 
         rand_nchoosek(rng, full, sample, complement);
         for (size_t i = 0; i < test_size; ++i) idx[rep * test_size + i] = static_cast<int64_t>(complement[i]);
     }
-    return Residual(run_folds(_data->X, _data->Y, _data->N, _data->K, _data->M, A, idx, test_size, num_trials), "LSO");
+    std::shared_ptr<const ValidationSummary> summary;
+    const std::vector<Mat2D> Ev = run_folds(_data->X, _data->Y, _data->N, _data->K, _data->M, A, idx, test_size, num_trials, summary);
+    return Residual(Ev, "LSO", summary);
 }
 
 // ---------------------------------------------------------------------------------------------

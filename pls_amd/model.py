@@ -13,6 +13,7 @@ by the HIP kernels behind the C-ABI.
 from __future__ import annotations
 
 import ctypes
+import sys
 
 import numpy as np
 
@@ -25,6 +26,7 @@ except Exception:  # pragma: no cover
 
 KERNEL_TYPE1 = L.KERNEL_TYPE1
 KERNEL_TYPE2 = L.KERNEL_TYPE2
+RESS, MSE = 0, 1  # PLS::VALIDATION_OUTPUT, reference include/PLS/pls.h:143
 
 
 def _is_torch(x) -> bool:
@@ -73,6 +75,18 @@ def _np_f(x, dtype):
     if a.ndim == 1:
         a = a[:, None]
     return np.asfortranarray(a, dtype=dtype)
+
+
+def pick_components(probw, ref, alpha: float = 0.1):
+    """per response: 1 + the first alt < ref[m] with probw[m, alt] > alpha, else ref[m] + 1 (src/pls.cpp:278-287) from
+    the probw (M x A) and 0-based ref (M) of Handle.validation"""
+    probw, ref = np.asarray(probw), np.asarray(ref, dtype=np.int64)
+    best = ref + 1
+    for m, r in enumerate(ref):
+        hits = np.flatnonzero(probw[m, :r] > alpha)
+        if hits.size:
+            best[m] = hits[0] + 1
+    return best
 
 
 # ---------------------------------------------------------------------------------------------
@@ -306,6 +320,36 @@ class Handle:
                                         L.F64 if dt == np.float64 else L.F32, L.MEM_HOST, p(E))
         L.check(rc, self.h)
         return E.transpose(0, 2, 1)
+
+    def validation(self, E):
+        """(press, D, probw, ref) of cross-validation residuals E, shape (M, nobs, A) as cv_folds returns them
+        (pls_hip_validation): press (M, A) = column sums of squares, ref (M,) int64 = 0-based column of the PRESS minimum,
+        D / probw (M, A) = Wilcoxon signed-rank sum and p-value of every alt < ref[m] against column ref[m] (0 / NaN
+        elsewhere).  A torch CUDA tensor stays on the device (the permuted view cv_folds returns is passed on without a
+        copy), numpy goes through the library's host path.  Local on a row-sharded handle: no message is sent."""
+        if _is_torch(E):
+            E = E if E.dim() == 3 else E[None]
+            M, nobs, A = E.shape
+            base = E.permute(0, 2, 1)  # the C layout: (M, A, nobs) contiguous
+            if base.dtype != torch.float64 or not base.is_contiguous():
+                base = base.to(torch.float64).contiguous()
+            press, D, probw = (colmajor_empty(M, A, torch.float64, E.device, ld=M) for _ in range(3))
+            ref = torch.empty(M, dtype=torch.int64, device=E.device)
+            rc = self._lib.pls_hip_validation(self.h, base.data_ptr(), nobs, A, M, L.MEM_DEVICE, press.data_ptr(),
+                                              D.data_ptr(), probw.data_ptr(), ref.data_ptr())
+            L.check(rc, self.h)
+            self._last_inputs = (base,)
+            return press, D, probw, ref
+        a = np.asarray(E)
+        a = a if a.ndim == 3 else a[None]
+        M, nobs, A = a.shape
+        base = np.ascontiguousarray(a.transpose(0, 2, 1), dtype=np.float64)
+        press, D, probw = (np.zeros((M, A), order="F") for _ in range(3))
+        ref = np.zeros(M, dtype=np.int64)
+        p = lambda x: x.ctypes.data_as(ctypes.c_void_p)
+        L.check(self._lib.pls_hip_validation(self.h, p(base), nobs, A, M, L.MEM_HOST, p(press), p(D), p(probw), p(ref)),
+                self.h)
+        return press, D, probw, ref
 
     def synth_x(self, row0: int, nrows: int, K: int, seed: int, dtype=None, device=None):
         dtype = dtype or torch.float64
@@ -595,6 +639,40 @@ class Model:
         Y2 = _np_f(Y_new, np.float64)
         fit = np.cumsum(np.asarray(S, dtype=np.float64)[:, :, None] * np.asarray(self.Q).T[None, :, :], axis=1)
         return (Y2[:, None, :] - fit).transpose(2, 0, 1)
+
+    # ---- model selection (reference include/PLS/pls.h:143-150, src/pls.cpp:235-305) ----------------------
+    # E is what cv_LOO / cv_LSO / cv_NEW_DATA return.
+    def validation(self, E, out_type: int):
+        """M x A: RESS = sum of squared residuals per (response, component count), MSE = RESS / nobs"""
+        if out_type not in (RESS, MSE):
+            raise L.PlsHipError(L.ERR_INVALID, f"out_type={out_type}: RESS or MSE")
+        press = self.handle.validation(E)[0]
+        return press / E.shape[-2] if out_type == MSE else press
+
+    def optimal_num_components(self, E, alpha: float = 0.1):
+        """per response: the smallest number of components whose errors a Wilcoxon signed-rank test (level alpha) cannot
+        tell from those at the PRESS minimum; component counts from 1 (src/pls.cpp:265-289).  Ties in |del| rank in row
+        order (INTEGRATION.md)."""
+        _, _, probw, ref = self.handle.validation(E)
+        if _is_torch(probw):
+            probw, ref = probw.cpu().numpy(), ref.cpu().numpy()
+        return pick_components(probw, ref, alpha)
+
+    def print_validation(self, E, label: str, out_type: int = MSE, file=None):
+        """the lines of print_validation (src/pls.cpp:291-305); `label` is Residual::method() there ("LOO", "LSO", ...)"""
+        file = sys.stderr if file is None else file
+        em = self.validation(E, out_type)
+        em = em.cpu().numpy() if _is_torch(em) else np.asarray(em)
+        name = "RMSE " if out_type == MSE else "PRESS "
+        if out_type == MSE:
+            em = np.sqrt(em)
+        txt = [[f"{v:.6g}" for v in row] for row in em]
+        wd = max(len(t) for row in txt for t in row)
+        print(f"{label} Validation:", file=file)
+        print(f"{name} Matrix (rows = Y variable; cols = # of components):", file=file)
+        print("\n".join(" ".join(t.rjust(wd) for t in row) for row in txt), file=file)
+        print("Optimal number of components (by Y variable):\t" +
+              " ".join(str(int(b)) for b in self.optimal_num_components(E)), file=file)
 
     def explained_variance_by_components(self, X, Y):
         """(EV, SSE), each M x A: what print_explained_variance (src/pls.cpp:551-562) reports for
