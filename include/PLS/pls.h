@@ -139,6 +139,15 @@ void print_validation(const Residual &residual, const VALIDATION_OUTPUT out_type
 struct DeviceContext;
 void set_devices(const std::vector<int> &devices);
 
+// ---- X-space diagnostics (extension; pls_hip_x_diagnostics in pls_hip.h) -------------------------
+// For 1..A components: Q(i, c-1) = squared distance of row i from the model plane (Q residual, SPE),
+// T2(i, c-1) = Hotelling's T^2 of its scores against the variance of the TRAINING scores, R2X[c-1] = share of
+// sum X^2 the first c components reproduce.
+struct XDiagnostics {
+    Mat2D Q, T2;
+    Row R2X;
+};
+
 // ---- the regression object -----------------------------------------------------------------
 // X: N x K predictors, Y: N x M responses, A components.
 // W (K x A) weights, P (K x A) X-loadings, Q (M x A) Y-loadings, R (K x A) weights that map the
@@ -181,6 +190,9 @@ struct Model {
     Residual cv_NEW_DATA(const Mat2D &X, const Mat2D &Y) const;
     Residual cv_LSO(const float_type test_fraction, const size_t num_trials, std::mt19937 &rng) const;
 
+    // Q residuals, Hotelling T^2 and R^2 X of X_new (preprocessed as the training data was: no centring here)
+    XDiagnostics x_diagnostics(const Mat2D &X_new) const;
+
     void print_explained_variance(const Mat2D &X, const Mat2D &Y, std::ostream &os = std::cerr) const;
     void print_state(std::ostream &os = std::cerr) const;
 
@@ -197,6 +209,10 @@ private:
     Mat2Dc P, W, R, Q;
     PLS::METHOD method;
     void fit_resident(const Resident &d, const METHOD &algorithm);
+    // t_a^T t_a / (N - 1) of the scores of the data the model was last fitted on (x_diagnostics); found on first use from
+    // the constructor's data, at once after a plsr() on other data (which does not stay resident)
+    mutable std::shared_ptr<const std::vector<float_type>> _tvar;
+    std::vector<float_type> training_tvar(const Resident &d) const;
 
     // shape-only models used by cv_LSO: no data yet, plsr() is called per trial
     Model(const size_t &num_predictors, const size_t &num_responses, const METHOD &algorithm = KERNEL_TYPE1);

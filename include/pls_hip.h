@@ -126,7 +126,8 @@ typedef enum {
  * replica-divergence guard (checksums of W, P, Q, R, B; the environment switch
  * PLS_HIP_REPLICA_GUARD=0, which must be set identically on EVERY rank, removes it).
  * KERNEL_TYPE2 / GRAM add one message of 8*K*K (X^T X); pls_hip_colwise_z_scores sends two
- * of 8*K, pls_hip_sse_by_components one of 8*A*M per range of component counts.
+ * of 8*K, pls_hip_sse_by_components one of 8*A*M per range of component counts,
+ * pls_hip_x_diagnostics exactly one of 8*(2*A+1) per call ([ssx (A+1), sst (A)], whichever outputs were asked for).
  * pls_hip_cv_folds sends, in this order: the partition (8*nranks: each rank's row count in
  * its own slot); on its batched route X^T X (8*K*K) and X^T Y (8*K*M) of all rows; the
  * held-out rows (8*rows*(K+M) per message of whole folds, rows*(K+M) capped at 2^20 unless a
@@ -305,6 +306,31 @@ PLS_HIP_API int pls_hip_cv_folds(pls_hip_handle h, const void *X, int64_t ldx, c
 PLS_HIP_API int pls_hip_validation(pls_hip_handle h, const double *E, int64_t nobs, int64_t A, int64_t M, int mem,
                                    double *PRESS, double *D, double *probw, int64_t *ref);
 
+/*
+ * X-space diagnostics of a model (R, P: K x A, ld K, fp64) on data X (N x K, as given: no centring is done here) for every
+ * component count c = 1..A in one call.  With S = X R and F_c = X - S[:, :c] P[:, :c]^T:
+ *   Qres (N x A, ld ldq)   Qres[i, c-1] = sum_k F_c[i,k]^2          the Q residual (SPE) of row i
+ *   T2   (N x A, ld ldt2)  T2[i, c-1]   = sum_{a<c} S[i,a]^2 / tvar[a]   Hotelling T^2; tvar[a] = t_a^T t_a / (n_train - 1)
+ *   S    (N x A, ld lds)   the scores, in the storage dtype of the call
+ *   ssx  (A + 1)           ssx[0] = sum X^2, ssx[c] = sum_i Qres[i, c-1]:  R^2 X_c = 1 - ssx[c] / ssx[0]
+ *   sst  (A)               sst[a] = sum_i S[i,a]^2
+ * F_c is formed explicitly, component by component in fp64, and then squared (no expansion of the square: it cancels).
+ * The scores are fp64 inside the library for either storage dtype.  Any of Qres, T2, S, ssx, sst may be NULL and work
+ * nobody asked for is not done: X is read once for the scores and, when Qres or ssx is wanted, once more per 24 component
+ * counts by the residual sweep.  tvar == NULL: X is the training set, tvar[a] = sst[a] / (n_total - 1) from this call's own
+ * scores (T2 then needs n_total >= 2).  A zero or non-finite tvar[a] gives inf/NaN in T2 from column a on.
+ * mem says where X, R, P, tvar and every output live.  DEVICE: the work is enqueued on the handle's stream, nothing returns
+ * to the host.  HOST: through the pinned staging pipeline, the call returns with the results in place.
+ * N >= 1 (0 on a rank of a sharded handle), 1 <= A <= K, A <= 2^20, K <= 2^30.  Fixed summation order: two calls with the
+ * same arguments return the same bits.
+ * Row-sharded handle (a reducer installed): a COLLECTIVE.  Qres, T2, S are the rank's own rows, n_total = rows over all
+ * ranks; ssx and sst are summed over the ranks in one message and every rank ends with identical bits.
+ */
+PLS_HIP_API int pls_hip_x_diagnostics(pls_hip_handle h, const void *X, int64_t ldx, int64_t N, int64_t n_total,
+                                      int64_t K, int64_t A, const double *R, const double *P, const double *tvar,
+                                      int dtype, int mem, double *Qres, int64_t ldq, double *T2, int64_t ldt2, void *S,
+                                      int64_t lds, double *ssx, double *sst);
+
 /* ---- synthetic inputs, generated on the device (DESIGN.md "Synthetic inputs") ------ */
 
 /* rows [row0, row0+nrows) of the global matrix -> X (nrows x K, ld ldx) / Y (nrows x M) */
@@ -408,6 +434,11 @@ PLS_HIP_API int pls_hip_group_xb(pls_hip_group g, pls_hip_matrix X, const double
 /* pls_hip_model_sse on resident data; R, Q, SSE (M x A) HOST */
 PLS_HIP_API int pls_hip_group_model_sse(pls_hip_group g, pls_hip_matrix X, pls_hip_matrix Y, int64_t A,
                                         const double *R, const double *Q, double *SSE);
+/* pls_hip_x_diagnostics on a resident X; R, P (K x A), tvar (A, or NULL: X is the training set), ssx (A + 1), sst (A) HOST;
+ * Qres, T2 (fp64) and S (dtype of X) resident N x A matrices.  Any output may be NULL. */
+PLS_HIP_API int pls_hip_group_x_diagnostics(pls_hip_group g, pls_hip_matrix X, int64_t A, const double *R, const double *P,
+                                            const double *tvar, pls_hip_matrix Qres, pls_hip_matrix T2, pls_hip_matrix S,
+                                            double *ssx, double *sst);
 /* pls_hip_cv_folds on resident data, E (M x nobs x A) HOST.  Groups of one member only (the fold kernel works on
  * K-sized data of ONE device); PLS_HIP_ERR_UNSUPPORTED otherwise. */
 PLS_HIP_API int pls_hip_group_cv_folds(pls_hip_group g, pls_hip_matrix X, pls_hip_matrix Y, int64_t A,

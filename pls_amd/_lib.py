@@ -74,6 +74,8 @@ PROTOTYPES = [
     ("pls_hip_model_sse", _int, [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _int, _int, _vp]),
     ("pls_hip_cv_folds", _int, [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _int, _int, _vp]),
     ("pls_hip_validation", _int, [_vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp]),
+    ("pls_hip_x_diagnostics", _int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _int, _int, _vp, _i64, _vp, _i64,
+                                     _vp, _i64, _vp, _vp]),
     ("pls_hip_synth_x", _int, [_vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_uint64, _int]),
     ("pls_hip_synth_y", _int, [_vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_uint64, _int]),
     # one process, several GPUs: groups and resident matrices
@@ -100,6 +102,7 @@ PROTOTYPES = [
     ("pls_hip_group_fit", _int, [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("pls_hip_group_xb", _int, [_vp, _vp, _vp, _i64, _i64, _vp]),
     ("pls_hip_group_model_sse", _int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    ("pls_hip_group_x_diagnostics", _int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("pls_hip_group_cv_folds", _int, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp]),
 ]
 

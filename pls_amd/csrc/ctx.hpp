@@ -32,6 +32,7 @@ struct pls_hip_context {
     hipGraphExec_t graph_exec = nullptr;
     DevBuf zeros, part, sspart, xbpart, wide1, red, red2, xx, xyp, praw, xy, v, cs, coop, lm, gxx, gxy, tab, work, cvidx, cvx, cvy, cvws, cve, cvtx, cvty, cvtt, cvm, cvkeep, cvred, hX, hY, hT, hW, hP, hQ, hR, hB, hIn, hOut;
     DevBuf valout, valpart, vale, valacc, valkeys, valhist;  // pls_hip_validation (plan_validation.hpp)
+    DevBuf xdS, xdQ, xdPT, xdred, xdtv, xdoQ, xdoT, xdoS, xdsmall;  // pls_hip_x_diagnostics (plan_xdiag.hpp): scores, column-block sums, the message, tvar, host staging
     i64 opt_val_lds_rows = -1;  // PLS_HIP_OPT_VALIDATION_LDS_ROWS; -1 = the device's own limit
     i64 val_lds_rows_dev = -1;  // that limit, found on first use
     std::string err;

@@ -718,6 +718,39 @@ int pls_hip_group_model_sse(pls_hip_group g, pls_hip_matrix X, pls_hip_matrix Y,
     });
 }
 
+int pls_hip_group_x_diagnostics(pls_hip_group g, pls_hip_matrix X, int64_t A, const double *R, const double *P,
+                                const double *tvar, pls_hip_matrix Qres, pls_hip_matrix T2, pls_hip_matrix S, double *ssx,
+                                double *sst) {
+    if (!g) return PLS_HIP_ERR_INVALID;
+    if (!same_partition(g, X) || !R || !P || A < 1 || A > X->K)
+        return gfail(g, PLS_HIP_ERR_INVALID, "bad group_x_diagnostics arguments");
+    for (pls_hip_matrix m : {Qres, T2, S}) {
+        if (!m) continue;
+        if (!same_partition(g, m) || m->N != X->N || m->K < A || m->dtype != (m == S ? X->dtype : PLS_HIP_F64))
+            return gfail(g, PLS_HIP_ERR_INVALID, "group_x_diagnostics: Qres, T2 (fp64) and S (storage type of X) must be resident N x A");
+    }
+    const i64 K = X->K;
+    return run_members(g, [&](int r) -> int {
+        pls_hip_context *c = g->h[r];
+        CHK(ensure(c, c->hR, (size_t)K * A * 8));
+        CHK(ensure(c, c->hP, (size_t)K * A * 8));
+        CHK(ensure(c, c->xdsmall, (size_t)(3 * A + 1) * 8));
+        double *small = (double *)c->xdsmall.p;
+        CHK(h2d(c, c->hR.p, K, R, K, K, A, 8));
+        CHK(h2d(c, c->hP.p, K, P, K, K, A, 8));
+        if (tvar) CHK(h2d(c, small, A, tvar, A, A, 1, 8));
+        CHK(pls_hip_x_diagnostics(c, X->data[r], X->ld[r], X->nrows[r], X->N, K, A, (const double *)c->hR.p, (const double *)c->hP.p,
+                                  tvar ? small : nullptr, X->dtype, PLS_HIP_MEM_DEVICE, Qres ? (double *)Qres->data[r] : nullptr,
+                                  Qres ? Qres->ld[r] : 1, T2 ? (double *)T2->data[r] : nullptr, T2 ? T2->ld[r] : 1,
+                                  S ? S->data[r] : nullptr, S ? S->ld[r] : 1, ssx ? small + A : nullptr,
+                                  sst ? small + 2 * A + 1 : nullptr));
+        if (r == 0 && ssx) CHK(d2h(c, ssx, A + 1, small + A, A + 1, A + 1, 1, 8));
+        if (r == 0 && sst) CHK(d2h(c, sst, A, small + 2 * A + 1, A, A, 1, 8));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return PLS_HIP_OK;
+    });
+}
+
 int pls_hip_group_cv_folds(pls_hip_group g, pls_hip_matrix X, pls_hip_matrix Y, int64_t A, const int64_t *test_idx,
                            int64_t test_size, int64_t num_folds, double *E) {
     if (!g) return PLS_HIP_ERR_INVALID;

@@ -32,6 +32,7 @@
 #include "syrk_kernels.hpp"
 #include "cv_kernels.hpp"
 #include "validation_kernels.hpp"
+#include "xdiag_kernels.hpp"
 #include "synth_kernels.hpp"
 #include "host_pipeline.hpp"
 #include "exchange_kernels.hpp"
@@ -45,6 +46,7 @@ using plsk::i64;
 #include "plan_fit.hpp"
 #include "host_entry.hpp"
 #include "plan_validation.hpp"
+#include "plan_xdiag.hpp"
 
 // =============================================================================================
 // C-ABI
@@ -105,7 +107,7 @@ int pls_hip_destroy(pls_hip_handle h) {
     DevBuf *bufs[] = {&h->tailcnt, &h->resident, &h->rgflags, &h->zeros, &h->part, &h->sspart, &h->xbpart, &h->wide1, &h->red, &h->red2, &h->xx, &h->xyp, &h->praw, &h->xy, &h->v, &h->cs, &h->coop, &h->lm, &h->gxx, &h->gxy, &h->tab,
                       &h->cvidx, &h->cvx, &h->cvy, &h->cvws, &h->cve, &h->cvtx, &h->cvty, &h->cvtt, &h->cvm, &h->cvkeep, &h->cvred, &h->work, &h->hX, &h->hY,
                       &h->hT, &h->hW, &h->hP, &h->hQ, &h->hR, &h->hB, &h->hIn, &h->hOut, &h->valout, &h->valpart, &h->vale, &h->valacc, &h->valkeys,
-                      &h->valhist};
+                      &h->valhist, &h->xdS, &h->xdQ, &h->xdPT, &h->xdred, &h->xdtv, &h->xdoQ, &h->xdoT, &h->xdoS, &h->xdsmall};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (void *q : h->graveyard) (void)hipFree(q);
@@ -648,6 +650,67 @@ int pls_hip_validation(pls_hip_handle h, const double *E, int64_t nobs, int64_t 
     CHK(set_device(h));
     // (local on a row-sharded handle: every rank holds the same E, nothing is exchanged)
     return validation_impl(h, E, nobs, (int)A, (int)M, mem, PRESS, D, probw, ref);
+}
+
+int pls_hip_x_diagnostics(pls_hip_handle h, const void *X, int64_t ldx, int64_t N, int64_t n_total, int64_t K, int64_t A,
+                          const double *R, const double *P, const double *tvar, int dtype, int mem, double *Qres, int64_t ldq,
+                          double *T2, int64_t ldt2, void *S, int64_t lds, double *ssx, double *sst) {
+    CHK(check_handle(h));
+    if (dtype != PLS_HIP_F64 && dtype != PLS_HIP_F32) return fail(h, PLS_HIP_ERR_INVALID, "bad dtype");
+    if (mem != PLS_HIP_MEM_HOST && mem != PLS_HIP_MEM_DEVICE) return fail(h, PLS_HIP_ERR_INVALID, "bad mem kind");
+    const bool empty_member = (N == 0 && h->nranks > 1);  // an empty shard still takes part in the message
+    const i64 n1 = std::max<i64>(N, 1);
+    if (N < 0 || (N == 0 && !empty_member) || n_total < N || n_total < 1 || K < 1 || A < 1 || A > K || A > (1 << 20) ||
+        K > (1 << 30) || (N > 0 && !X) || !R || !P || ldx < n1 || (Qres && ldq < n1) || (T2 && ldt2 < n1) || (S && lds < n1))
+        return fail(h, PLS_HIP_ERR_INVALID, "bad x_diagnostics arguments");
+    if (T2 && !tvar && n_total < 2) return fail(h, PLS_HIP_ERR_INVALID, "x_diagnostics: T2 from the call's own scores needs n_total >= 2");
+    CHK(set_device(h));
+    const size_t es = esize(dtype);
+    const void *dX = X;
+    const double *dR = R, *dP = P, *dtv = tvar;
+    double *dQ = Qres, *dT2 = T2, *dssx = ssx, *dsst = sst;
+    void *dS = S;
+    i64 dldx = ldx, dldq = ldq, dldt2 = ldt2, dlds = lds;
+    if (mem == PLS_HIP_MEM_HOST) {
+        const i64 ldn = n1 + (n1 & 1);
+        CHK(ensure(h, h->hIn, (size_t)ldn * K * es));
+        CHK(ensure(h, h->hR, (size_t)K * A * 8));
+        CHK(ensure(h, h->hP, (size_t)K * A * 8));
+        CHK(ensure(h, h->xdsmall, (size_t)(3 * A + 1) * 8));  // [tvar (A), ssx (A + 1), sst (A)]
+        if (Qres) CHK(ensure(h, h->xdoQ, (size_t)ldn * A * 8));
+        if (T2) CHK(ensure(h, h->xdoT, (size_t)ldn * A * 8));
+        if (S) CHK(ensure(h, h->xdoS, (size_t)ldn * A * es));
+        CHK(h2d(h, h->hIn.p, ldn, X, ldx, N, K, es));
+        CHK(h2d(h, h->hR.p, K, R, K, K, A, 8));
+        CHK(h2d(h, h->hP.p, K, P, K, K, A, 8));
+        double *small = (double *)h->xdsmall.p;
+        if (tvar) CHK(h2d(h, small, A, tvar, A, A, 1, 8));
+        dX = h->hIn.p; dR = (const double *)h->hR.p; dP = (const double *)h->hP.p;
+        dtv = tvar ? small : nullptr;
+        dQ = Qres ? (double *)h->xdoQ.p : nullptr;
+        dT2 = T2 ? (double *)h->xdoT.p : nullptr;
+        dS = S ? h->xdoS.p : nullptr;
+        dssx = ssx ? small + A : nullptr;
+        dsst = sst ? small + 2 * A + 1 : nullptr;
+        dldx = dldq = dldt2 = dlds = ldn;
+    }
+    int rc;
+    if (dtype == PLS_HIP_F64)
+        rc = xdiag_device<double>(h, (const double *)dX, dldx, N, n_total, (int)K, (int)A, dR, dP, dtv, dQ, dldq, dT2, dldt2,
+                                  (double *)dS, dlds, dssx, dsst);
+    else
+        rc = xdiag_device<float>(h, (const float *)dX, dldx, N, n_total, (int)K, (int)A, dR, dP, dtv, dQ, dldq, dT2, dldt2,
+                                 (float *)dS, dlds, dssx, dsst);
+    if (rc != PLS_HIP_OK) return rc;
+    if (mem == PLS_HIP_MEM_HOST) {
+        if (Qres) CHK(d2h(h, Qres, ldq, dQ, dldq, N, A, 8));
+        if (T2) CHK(d2h(h, T2, ldt2, dT2, dldt2, N, A, 8));
+        if (S) CHK(d2h(h, S, lds, dS, dlds, N, A, es));
+        if (ssx) CHK(d2h(h, ssx, A + 1, dssx, A + 1, A + 1, 1, 8));
+        if (sst) CHK(d2h(h, sst, A, dsst, A, A, 1, 8));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return PLS_HIP_OK;
 }
 
 int pls_hip_synth_x(pls_hip_handle h, void *X, int64_t ldx, int64_t row0, int64_t nrows, int64_t K,

@@ -537,6 +537,7 @@ void Model::plsr(const Mat2D &X, const Mat2D &Y, const METHOD &algorithm) {
         upload_pair(X, Y, d.X, d.Y);
     }
     fit_resident(d, algorithm);
+    _tvar = std::make_shared<const std::vector<float_type>>(training_tvar(d));
 }
 
 void Model::fit_resident(const Resident &d, const METHOD &algorithm) {
@@ -559,6 +560,7 @@ void Model::fit_resident(const Resident &d, const METHOD &algorithm) {
               "pls_hip_group_fit");
     }
     _scores = sc;
+    _tvar.reset();
     W = to_complex(w, K, Ai);
     P = to_complex(p, K, Ai);
     R = to_complex(r, K, Ai);
@@ -754,6 +756,51 @@ Residual Model::cv_LSO(const float_type test_fraction, const size_t num_trials, 
     std::shared_ptr<const ValidationSummary> summary;
     const std::vector<Mat2D> Ev = run_folds(_data->X, _data->Y, _data->N, _data->K, _data->M, A, idx, test_size, num_trials, summary);
     return Residual(Ev, "LSO", summary);
+}
+
+// ---------------------------------------------------------------------------------------------
+// X-space diagnostics (extension): one call into the device library for every component count
+// ---------------------------------------------------------------------------------------------
+std::vector<float_type> Model::training_tvar(const Resident &d) const {
+    const Index Ai = static_cast<Index>(A);
+    const std::vector<float_type> r = real_part(R, Ai), p = real_part(P, Ai);
+    std::vector<float_type> tv(static_cast<size_t>(Ai));
+    const Ctx &ctx = d.X.ctx;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    check(ctx, pls_hip_group_x_diagnostics(ctx->g, d.X.m, Ai, r.data(), p.data(), nullptr, nullptr, nullptr, nullptr, nullptr, tv.data()),
+          "pls_hip_group_x_diagnostics");
+    for (float_type &v : tv) v /= static_cast<float_type>(d.N - 1);  // (one training row: inf / NaN, as a variance of one value is)
+    return tv;
+}
+
+XDiagnostics Model::x_diagnostics(const Mat2D &X_new) const {
+    if (X_new.cols() != R.rows()) throw std::invalid_argument("PLS::Model::x_diagnostics: column count differs from the training data");
+    if (!_tvar) {
+        if (!_data) throw std::invalid_argument("PLS::Model::x_diagnostics: the model holds no training data");
+        _tvar = std::make_shared<const std::vector<float_type>>(training_tvar(*_data));
+    }
+    const Index N = X_new.rows(), Ai = static_cast<Index>(A);
+    XDiagnostics out;
+    out.Q = Mat2D(N, Ai);
+    out.T2 = Mat2D(N, Ai);
+    out.R2X = Row::Zero(Ai);
+    if (N == 0) return out;
+    const std::vector<float_type> r = real_part(R, Ai), p = real_part(P, Ai);
+    std::vector<float_type> ssx(static_cast<size_t>(Ai + 1));
+    {
+        const Ctx ctx = _ctx ? _ctx : current_context();
+        ResidentMatrix dX(ctx), dQ(ctx), dT2(ctx);  // (released after the lock)
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        dX.upload(X_new);
+        dQ.alloc(N, Ai);
+        dT2.alloc(N, Ai);
+        check(ctx, pls_hip_group_x_diagnostics(ctx->g, dX.m, Ai, r.data(), p.data(), _tvar->data(), dQ.m, dT2.m, nullptr, ssx.data(), nullptr),
+              "pls_hip_group_x_diagnostics");
+        check(ctx, pls_hip_group_download(ctx->g, dQ.m, 0, Ai, out.Q.data(), N), "pls_hip_group_download");
+        check(ctx, pls_hip_group_download(ctx->g, dT2.m, 0, Ai, out.T2.data(), N), "pls_hip_group_download");
+    }
+    for (Index c = 0; c < Ai; ++c) out.R2X[c] = 1.0 - ssx[static_cast<size_t>(c + 1)] / ssx[0];
+    return out;
 }
 
 // ---------------------------------------------------------------------------------------------

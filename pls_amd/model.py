@@ -351,6 +351,61 @@ class Handle:
                 self.h)
         return press, D, probw, ref
 
+    def x_diagnostics(self, X, R, P, tvar=None, want=("Q", "T2", "ssx"), n_total: int | None = None):
+        """X-space diagnostics of a model (R, P: K x A) on data X (N x K) for every component count 1..A
+        (pls_hip_x_diagnostics).  `want` picks from "Q" (Q residuals, N x A), "T2" (Hotelling T^2, N x A), "S" (scores,
+        N x A in the dtype of X), "ssx" (A + 1: sum X^2, then the sums of the Q columns), "sst" (A: column sums of squares of
+        the scores); the result is a dict of those.  tvar (A) = t_a^T t_a / (n_train - 1) of the training scores; None means
+        X IS the training data.  Torch CUDA tensors stay on the device, numpy arrays take the library's host path.
+        Row-sharded handle: a collective, n_total = rows over all ranks."""
+        want = set(want)
+        bad = want - {"Q", "T2", "S", "ssx", "sst"}
+        if bad:
+            raise L.PlsHipError(L.ERR_INVALID, f"x_diagnostics: unknown output(s) {sorted(bad)}")
+        if _is_torch(X):
+            X = as_colmajor(X)
+            N, K = X.shape
+            dev, f64 = X.device, torch.float64
+            R = as_colmajor(R.to(f64)); P = as_colmajor(P.to(f64))
+            A = R.shape[1]
+            if _ld(R) != K:
+                R = colmajor_empty(K, A, f64, dev, ld=K).copy_(R)
+            if _ld(P) != K:
+                P = colmajor_empty(K, A, f64, dev, ld=K).copy_(P)
+            tv = None if tvar is None else torch.as_tensor(tvar, dtype=f64, device=dev).contiguous()
+            out = {}
+            if "Q" in want: out["Q"] = colmajor_empty(N, A, f64, dev)
+            if "T2" in want: out["T2"] = colmajor_empty(N, A, f64, dev)
+            if "S" in want: out["S"] = colmajor_empty(N, A, X.dtype, dev)
+            if "ssx" in want: out["ssx"] = torch.empty(A + 1, dtype=f64, device=dev)
+            if "sst" in want: out["sst"] = torch.empty(A, dtype=f64, device=dev)
+            ptr = lambda k: out[k].data_ptr() if k in out else None
+            ldo = lambda k: _ld(out[k]) if k in out else 1
+            rc = self._lib.pls_hip_x_diagnostics(self.h, X.data_ptr(), _ld(X), N, n_total or N, K, A, R.data_ptr(), P.data_ptr(),
+                                                 tv.data_ptr() if tv is not None else None, self._dt(X), L.MEM_DEVICE,
+                                                 ptr("Q"), ldo("Q"), ptr("T2"), ldo("T2"), ptr("S"), ldo("S"), ptr("ssx"), ptr("sst"))
+            L.check(rc, self.h)
+            self._last_inputs = (X, R, P, tv)
+            return out
+        dt = np.float32 if np.asarray(X).dtype == np.float32 else np.float64
+        X = _np_f(X, dt); R = _np_f(R, np.float64); P = _np_f(P, np.float64)
+        N, K = X.shape
+        A = R.shape[1]
+        tv = None if tvar is None else np.ascontiguousarray(tvar, dtype=np.float64)
+        out = {}
+        if "Q" in want: out["Q"] = np.zeros((N, A), order="F")
+        if "T2" in want: out["T2"] = np.zeros((N, A), order="F")
+        if "S" in want: out["S"] = np.zeros((N, A), dtype=dt, order="F")
+        if "ssx" in want: out["ssx"] = np.zeros(A + 1)
+        if "sst" in want: out["sst"] = np.zeros(A)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        ptr = lambda k: p(out[k]) if k in out else None
+        rc = self._lib.pls_hip_x_diagnostics(self.h, p(X), max(N, 1), N, n_total or N, K, A, p(R), p(P),
+                                             p(tv) if tv is not None else None, L.F64 if dt == np.float64 else L.F32, L.MEM_HOST,
+                                             ptr("Q"), max(N, 1), ptr("T2"), max(N, 1), ptr("S"), max(N, 1), ptr("ssx"), ptr("sst"))
+        L.check(rc, self.h)
+        return out
+
     def synth_x(self, row0: int, nrows: int, K: int, seed: int, dtype=None, device=None):
         dtype = dtype or torch.float64
         X = colmajor_empty(nrows, K, dtype, device or f"cuda:{self.device}")
@@ -525,6 +580,26 @@ class Group:
         self._check(self._lib.pls_hip_group_model_sse(self.g, X, Y, A, p(R), p(Q), p(sse)))
         return sse
 
+    def x_diagnostics(self, X, R, P, tvar=None, want=("Q", "T2", "ssx")):
+        """pls_hip_group_x_diagnostics on a resident X: dict with "Q", "T2", "S" as resident N x A matrices and "ssx", "sst"
+        as numpy vectors, whichever `want` names (see Handle.x_diagnostics)"""
+        want = set(want)
+        N, K, dt = self.shape(X)
+        R = _np_f(R, np.float64); P = _np_f(P, np.float64)
+        A = R.shape[1]
+        tv = None if tvar is None else np.ascontiguousarray(tvar, dtype=np.float64)
+        out = {}
+        if "Q" in want: out["Q"] = self.alloc(N, A, np.float64)
+        if "T2" in want: out["T2"] = self.alloc(N, A, np.float64)
+        if "S" in want: out["S"] = self.alloc(N, A, dt)
+        if "ssx" in want: out["ssx"] = np.zeros(A + 1)
+        if "sst" in want: out["sst"] = np.zeros(A)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        vec = lambda k: p(out[k]) if k in out else None
+        self._check(self._lib.pls_hip_group_x_diagnostics(self.g, X, A, p(R), p(P), p(tv) if tv is not None else None,
+                                                          out.get("Q"), out.get("T2"), out.get("S"), vec("ssx"), vec("sst")))
+        return out
+
     def cv_folds(self, X, Y, A: int, test_idx):
         idx = np.ascontiguousarray(np.asarray(test_idx, dtype=np.int64))
         if idx.ndim == 1:
@@ -570,6 +645,7 @@ class Model:
             dt = np.float32 if np.asarray(X).dtype == np.float32 else np.float64
             out = self.handle.fit_host(X, Y, self.A, algorithm, dtype=dt)
         self.W, self.P, self.Q, self.R, self.T = (out[k] for k in "WPQRT")
+        self._tvar_cache = None
 
     def _comp(self, comp):
         comp = self.A if comp is None else int(comp)
@@ -673,6 +749,37 @@ class Model:
         print("\n".join(" ".join(t.rjust(wd) for t in row) for row in txt), file=file)
         print("Optimal number of components (by Y variable):\t" +
               " ".join(str(int(b)) for b in self.optimal_num_components(E)), file=file)
+
+    # ---- X-space diagnostics (no counterpart in the reference) --------------------------------------------
+    def _tvar(self):
+        """t_a^T t_a / (N - 1) of the training scores: from T when the fit produced it, else (KERNEL_TYPE2) from one pass
+        over the training data"""
+        if getattr(self, "_tvar_cache", None) is None:
+            n = self._X.shape[0]
+            if self.T is not None:
+                T = self.T.to(torch.float64) if _is_torch(self.T) else np.asarray(self.T, dtype=np.float64)
+                self._tvar_cache = (T * T).sum(0) / (n - 1)
+            else:
+                sst = self.handle.x_diagnostics(self._X, self.R, self.P, want=("sst",))["sst"]
+                self._tvar_cache = sst / (n - 1)
+        return self._tvar_cache
+
+    def x_diagnostics(self, X_new=None):
+        """dict(Q, T2: N x A; R2X: A) for 1..A components: the Q residual (squared distance of a row from the model plane),
+        Hotelling's T^2 (its distance from the centre inside the plane, scaled by the variance of the TRAINING scores) and
+        the share of sum X^2 the components reproduce.  X_new=None: the training data.  New rows must be preprocessed as
+        the training data was (the model does no centring of its own)."""
+        X = self._X if X_new is None else X_new
+        tv = self._tvar()
+        if _is_torch(X) != _is_torch(tv):
+            tv = tv.cpu().numpy() if _is_torch(tv) else torch.as_tensor(tv, device=X.device)
+        R, P = self.R, self.P
+        if _is_torch(X) != _is_torch(R):
+            R, P = ((R.cpu().numpy(), P.cpu().numpy()) if _is_torch(R) else
+                    (torch.as_tensor(np.asarray(R), device=X.device), torch.as_tensor(np.asarray(P), device=X.device)))
+        out = self.handle.x_diagnostics(X, R, P, tvar=tv, want=("Q", "T2", "ssx"))
+        ssx = out["ssx"]
+        return dict(Q=out["Q"], T2=out["T2"], R2X=1.0 - ssx[1:] / ssx[0])
 
     def explained_variance_by_components(self, X, Y):
         """(EV, SSE), each M x A: what print_explained_variance (src/pls.cpp:551-562) reports for
