@@ -148,6 +148,15 @@ struct XDiagnostics {
     Row R2X;
 };
 
+// ---- response-permutation test (extension; pls_hip_fit_batch in pls_hip.h) ----------------------
+// r2y(m, c-1) = cumulative R^2 Y of response m with c components for Y itself, r2y_perm[b] the same for the rows of Y
+// permuted by perms[b], p(m, c-1) = (1 + #{b : r2y_perm[b](m, c-1) >= r2y(m, c-1)}) / (perms.size() + 1).
+struct PermutationTest {
+    Mat2D r2y;
+    std::vector<Mat2D> r2y_perm;
+    Mat2D p;
+};
+
 // ---- the regression object -----------------------------------------------------------------
 // X: N x K predictors, Y: N x M responses, A components.
 // W (K x A) weights, P (K x A) X-loadings, Q (M x A) Y-loadings, R (K x A) weights that map the
@@ -192,6 +201,11 @@ struct Model {
 
     // Q residuals, Hotelling T^2 and R^2 X of X_new (preprocessed as the training data was: no centring here)
     XDiagnostics x_diagnostics(const Mat2D &X_new) const;
+
+    // Is a model of this many components on (X, Y) better than chance?  Every perms[b] is a permutation of 0..N-1; problem
+    // b refits the KERNEL_TYPE2 model on (X, Y with row i taken from row perms[b][i]).  All refits share one X^T X and run
+    // as one batched call on the GPU.  X, Y preprocessed as for a fit (no centring here).
+    PermutationTest permutation_test(const Mat2D &X, const Mat2D &Y, const std::vector<Colsz> &perms) const;
 
     void print_explained_variance(const Mat2D &X, const Mat2D &Y, std::ostream &os = std::cerr) const;
     void print_state(std::ostream &os = std::cerr) const;

@@ -133,6 +133,10 @@ typedef enum {
  * held-out rows (8*rows*(K+M) per message of whole folds, rows*(K+M) capped at 2^20 unless a
  * single fold is larger); then E (8*len per piece of at most 2^20 of its values) on the
  * batched route, or the messages of one KERNEL_TYPE1 fit per fold on the refit route.
+ * pls_hip_fit_batch sends, in this order: X^T X (8*K*K); then, round by round, one message per piece of whole problems,
+ * [XY_b (K*M), ssy_b (M)] per problem: 8*(K+1)*M*nb values, (K+1)*M*nb capped at 2^20 unless a single problem is larger
+ * (a piece never spans two rounds).  On its per-problem route: the messages of one KERNEL_TYPE2 fit per problem, each followed
+ * by one of 8*M (ssy) when ssy is asked for.
  * Return 0 on success.
  */
 #define PLS_HIP_REDUCE_SLICES 8
@@ -172,6 +176,9 @@ PLS_HIP_API int pls_hip_get_option(pls_hip_handle h, int option, int64_t *value)
 /* Row-sharded fit over `nranks` processes (one per GPU): every rank passes its own row
  * block and the same K, M, A; fn sums the small partial products.  fn == NULL: single rank. */
 PLS_HIP_API int pls_hip_set_reducer(pls_hip_handle h, pls_hip_allreduce_fn fn, void *user, int rank, int nranks);
+/* What pls_hip_set_reducer left: *installed = 1 when a reducer function is set (the handle's calls are collectives), and the
+ * handle's rank and nranks.  Any of the three pointers may be NULL. */
+PLS_HIP_API int pls_hip_get_reducer(pls_hip_handle h, int *installed, int *rank, int *nranks);
 /* Optional caller-owned DEVICE staging buffer for the reducer
  * (>= PLS_HIP_REDUCE_SLICES * max(K*M, K+1) fp64), so a
  * host runtime can hand its collective a buffer it allocated itself. */
@@ -331,6 +338,40 @@ PLS_HIP_API int pls_hip_x_diagnostics(pls_hip_handle h, const void *X, int64_t l
                                       int dtype, int mem, double *Qres, int64_t ldq, double *T2, int64_t ldt2, void *S,
                                       int64_t lds, double *ssx, double *sst);
 
+/*
+ * Many response sets against ONE X: for every problem b = 0..nprob-1 the model Model::plsr(X, Y_b, KERNEL_TYPE2)
+ * (src/pls.cpp:390-437), Y_b = columns [b*M, (b+1)*M) of Ys (N x nprob*M, column-major, ld ldy).  All problems share
+ * XX = X^T X, formed once; each starts from its own XY_b = X^T Y_b, all of them formed in one wide product on the matrix
+ * cores.  This is the work behind a response-permutation (Y-randomisation) test, a scan of one model per phenotype, or any
+ * loop of pls_hip_fit(..., KERNEL_TYPE2) over the same X.  X and Ys use the storage dtype of the call (fp64 accumulation
+ * throughout) and are never written.  Outputs, all fp64, any may be NULL (work nobody asked for beyond the loop itself is not
+ * done):
+ *   R    R + b*K*A   K x A, ld K            Q    Q + b*M*A   M x A, ld M
+ *   tt   tt + b*A    tt[a] = r_a^T XX r_a   B    B + b*K*M   K x M, ld K, = R Q^T
+ *   ssy  ssy + b*M   sum_i Y_b[i,m]^2
+ * so that ESS[m,c] = sum_{a<=c} Q[m,a]^2 tt[a] and R^2 Y = ESS / ssy are host arithmetic on M*A numbers.  W, P and T are NOT
+ * returned: a caller who wants them for one problem calls pls_hip_fit on (X, Y_b).  Sign convention for M > 1: that of
+ * pls_hip_fit.  The algebra on X^T X squares the condition number of X.
+ * 1 <= A <= K, N >= 1 (0 on a rank of a sharded handle), M >= 1, nprob >= 1, ldx, ldy >= N, X and Ys non-NULL; anything else
+ * is PLS_HIP_ERR_INVALID before anything is written.
+ * mem == DEVICE: the call only enqueues work on the handle's stream.  mem == HOST: the inputs cross through the pinned staging
+ * pipeline and the call returns with the results in place.  Fixed summation order: two calls with the same arguments return
+ * the same bits.
+ * Batched route (K <= 16384, M <= 32, A <= 4096): the problems run in rounds of as many as 4 GB of workspace and half the
+ * free device memory hold (3 K A + K M + M A + K + 1 values per problem and the columns of the product); per component two
+ * launches for ALL problems of a round -- V = XX [r_0 r_1 ...] as one matrix-core GEMM, then one workgroup per problem.
+ * Per-problem route (every other shape, a workspace that does not fit, or PLS_HIP_BATCH_REFIT=1 in the environment): one
+ * KERNEL_TYPE2 fit per problem under the handle's plan -- same results to rounding, nprob fits; shapes pls_hip_fit refuses
+ * return its status.
+ * Row-sharded handle (a reducer installed): a COLLECTIVE with the same K, M, A, nprob on every rank; Ys holds the rank's
+ * own rows.  X^T X and the products of every piece of problems are summed over the ranks (pls_hip_allreduce_fn lists the
+ * messages), the component loops then run replicated from identical bits: every rank ends with identical outputs.
+ * PLS_HIP_BATCH_REFIT must be set alike on every rank.
+ */
+PLS_HIP_API int pls_hip_fit_batch(pls_hip_handle h, const void *X, int64_t ldx, const void *Ys, int64_t ldy,
+                                  int64_t N, int64_t K, int64_t M, int64_t A, int64_t nprob, int dtype, int mem,
+                                  double *R, double *Q, double *tt, double *B, double *ssy);
+
 /* ---- synthetic inputs, generated on the device (DESIGN.md "Synthetic inputs") ------ */
 
 /* rows [row0, row0+nrows) of the global matrix -> X (nrows x K, ld ldx) / Y (nrows x M) */
@@ -439,6 +480,10 @@ PLS_HIP_API int pls_hip_group_model_sse(pls_hip_group g, pls_hip_matrix X, pls_h
 PLS_HIP_API int pls_hip_group_x_diagnostics(pls_hip_group g, pls_hip_matrix X, int64_t A, const double *R, const double *P,
                                             const double *tvar, pls_hip_matrix Qres, pls_hip_matrix T2, pls_hip_matrix S,
                                             double *ssx, double *sst);
+/* pls_hip_fit_batch on resident X (N x K) and Ys (N x nprob*M, the storage type of X); R, Q, tt, B, ssy HOST, any may be NULL.
+ * The members run as for pls_hip_group_fit; an X^T X that came with pls_hip_group_upload_xy is used. */
+PLS_HIP_API int pls_hip_group_fit_batch(pls_hip_group g, pls_hip_matrix X, pls_hip_matrix Ys, int64_t M, int64_t A,
+                                        double *R, double *Q, double *tt, double *B, double *ssy);
 /* pls_hip_cv_folds on resident data, E (M x nobs x A) HOST.  Groups of one member only (the fold kernel works on
  * K-sized data of ONE device); PLS_HIP_ERR_UNSUPPORTED otherwise. */
 PLS_HIP_API int pls_hip_group_cv_folds(pls_hip_group g, pls_hip_matrix X, pls_hip_matrix Y, int64_t A,

@@ -59,6 +59,7 @@ PROTOTYPES = [
     ("pls_hip_set_option", _int, [_vp, _int, _i64]),
     ("pls_hip_get_option", _int, [_vp, _int, ctypes.POINTER(_i64)]),
     ("pls_hip_set_reducer", _int, [_vp, ALLREDUCE_FN, _vp, _int, _int]),
+    ("pls_hip_get_reducer", _int, [_vp, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int)]),
     ("pls_hip_set_reduce_buffer", _int, [_vp, _vp, _i64]),
     ("pls_hip_synchronize", _int, [_vp]),
     ("pls_hip_last_error", ctypes.c_char_p, [_vp]),
@@ -76,6 +77,7 @@ PROTOTYPES = [
     ("pls_hip_validation", _int, [_vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp]),
     ("pls_hip_x_diagnostics", _int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _int, _int, _vp, _i64, _vp, _i64,
                                      _vp, _i64, _vp, _vp]),
+    ("pls_hip_fit_batch", _int, [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     ("pls_hip_synth_x", _int, [_vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_uint64, _int]),
     ("pls_hip_synth_y", _int, [_vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_uint64, _int]),
     # one process, several GPUs: groups and resident matrices
@@ -103,6 +105,7 @@ PROTOTYPES = [
     ("pls_hip_group_xb", _int, [_vp, _vp, _vp, _i64, _i64, _vp]),
     ("pls_hip_group_model_sse", _int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     ("pls_hip_group_x_diagnostics", _int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("pls_hip_group_fit_batch", _int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     ("pls_hip_group_cv_folds", _int, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp]),
 ]
 

@@ -33,6 +33,7 @@ struct pls_hip_context {
     DevBuf zeros, part, sspart, xbpart, wide1, red, red2, xx, xyp, praw, xy, v, cs, coop, lm, gxx, gxy, tab, work, cvidx, cvx, cvy, cvws, cve, cvtx, cvty, cvtt, cvm, cvkeep, cvred, hX, hY, hT, hW, hP, hQ, hR, hB, hIn, hOut;
     DevBuf valout, valpart, vale, valacc, valkeys, valhist;  // pls_hip_validation (plan_validation.hpp)
     DevBuf xdS, xdQ, xdPT, xdred, xdtv, xdoQ, xdoT, xdoS, xdsmall;  // pls_hip_x_diagnostics (plan_xdiag.hpp): scores, column-block sums, the message, tvar, host staging
+    DevBuf bws, bv, bred, bmsg, bssy, bY, boR, boQ, bott, boB, bossy;  // pls_hip_fit_batch (plan_batch.hpp): per-problem workspace, V and r columns, the sliced product, the message, host staging
     i64 opt_val_lds_rows = -1;  // PLS_HIP_OPT_VALIDATION_LDS_ROWS; -1 = the device's own limit
     i64 val_lds_rows_dev = -1;  // that limit, found on first use
     std::string err;
@@ -85,9 +86,13 @@ struct pls_hip_context {
     //                            pass (2).  Default (unset): behind READ-ONLY passes only; behind a deflating sweep the tail's loads
     //                            queue behind the write drain and the update is faster as a launch of its own
     //                            (profiles/r5/tail_ab.txt)
+    //   PLS_HIP_BATCH_REFIT=1    pls_hip_fit_batch as one KERNEL_TYPE2 fit per problem (the general form; tests compare)
+    //   PLS_HIP_BATCH_ROUND=n    at most n problems per round of pls_hip_fit_batch's batched route (tests: several rounds)
     //   PLS_HIP_RESIDENT=0       mid-size single-response fits on the general plan instead of the one-launch resident fit
     //   PLS_HIP_REPLICA_GUARD=0  no replica-divergence check after a sharded fit (must be the same on every rank)
     struct Env {
+        bool batch_refit = false;
+        i64 batch_round = 0;
         bool tiny = true, cv_refit = false, tail = true, replica_guard = true, resident = true;
         int tail_update = 1;  // 0: never, 1: in the tail of READ-ONLY passes (default), 2: of every pass
         int xb4 = 1;          // PLS_HIP_XB4=0: X B with 5..32 columns on the older kernels

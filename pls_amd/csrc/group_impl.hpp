@@ -751,6 +751,40 @@ int pls_hip_group_x_diagnostics(pls_hip_group g, pls_hip_matrix X, int64_t A, co
     });
 }
 
+int pls_hip_group_fit_batch(pls_hip_group g, pls_hip_matrix X, pls_hip_matrix Ys, int64_t M, int64_t A, double *R, double *Q,
+                            double *tt, double *B, double *ssy) {
+    if (!g) return PLS_HIP_ERR_INVALID;
+    if (!same_partition(g, X) || !same_partition(g, Ys) || X->N != Ys->N || X->dtype != Ys->dtype || M < 1 || Ys->K % M != 0 ||
+        A < 1 || A > X->K)
+        return gfail(g, PLS_HIP_ERR_INVALID, "bad group_fit_batch arguments");
+    const i64 K = X->K, nprob = Ys->K / M;
+    return run_members(g, [&](int r) -> int {
+        pls_hip_context *c = g->h[r];
+        // every member derives every output (identical bits); member 0's are returned
+        if (R) CHK(ensure(c, c->boR, (size_t)nprob * K * A * 8));
+        if (Q) CHK(ensure(c, c->boQ, (size_t)nprob * M * A * 8));
+        if (tt) CHK(ensure(c, c->bott, (size_t)nprob * A * 8));
+        if (B) CHK(ensure(c, c->boB, (size_t)nprob * K * M * 8));
+        if (ssy) CHK(ensure(c, c->bossy, (size_t)nprob * M * 8));
+        if (X->gram_ok) c->pre_xx = X->gram_xx[r];  // X^T X of this member's rows came with the upload
+        const int rc = pls_hip_fit_batch(c, X->data[r], X->ld[r], Ys->data[r], Ys->ld[r], X->nrows[r], K, M, A, nprob, X->dtype,
+                                         PLS_HIP_MEM_DEVICE, R ? (double *)c->boR.p : nullptr, Q ? (double *)c->boQ.p : nullptr,
+                                         tt ? (double *)c->bott.p : nullptr, B ? (double *)c->boB.p : nullptr,
+                                         ssy ? (double *)c->bossy.p : nullptr);
+        c->pre_xx = nullptr;
+        CHK(rc);
+        if (r == 0) {
+            if (R) CHK(d2h(c, R, K * A, c->boR.p, K * A, K * A, nprob, 8));
+            if (Q) CHK(d2h(c, Q, M * A, c->boQ.p, M * A, M * A, nprob, 8));
+            if (tt) CHK(d2h(c, tt, A, c->bott.p, A, A, nprob, 8));
+            if (B) CHK(d2h(c, B, K * M, c->boB.p, K * M, K * M, nprob, 8));
+            if (ssy) CHK(d2h(c, ssy, M, c->bossy.p, M, M, nprob, 8));
+        }
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return PLS_HIP_OK;
+    });
+}
+
 int pls_hip_group_cv_folds(pls_hip_group g, pls_hip_matrix X, pls_hip_matrix Y, int64_t A, const int64_t *test_idx,
                            int64_t test_size, int64_t num_folds, double *E) {
     if (!g) return PLS_HIP_ERR_INVALID;

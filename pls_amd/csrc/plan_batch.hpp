@@ -1,0 +1,261 @@
+// plan_batch.hpp -- pls_hip_fit_batch: many response sets against one X.  The batched route (X^T X once, the wide X^T [Y_0 | Y_1 | ...]
+// on the matrix cores, two launches per component for all problems of a round) and the per-problem route (one KERNEL_TYPE2 fit each).
+// Part of libpls_hip.so: included by pls_hip.hip (one translation unit), in the order given there.
+#pragma once
+
+namespace {
+
+constexpr i64 BATCH_MSG_CAP = (i64)1 << 20;    // values per slice of a message of whole problems on a sharded handle
+constexpr i64 BATCH_ROUND_BYTES = (i64)4 << 30;  // workspace of one round
+constexpr int BATCH_CB = 32;                   // column block of the fallback product (launch_xty)
+
+// the batched route's shapes: the bounds of cv_folds_kernel (everything M-sized in one workgroup's LDS, X^T X resident)
+bool batch_covers(const pls_hip_context *c, i64 K, i64 M, i64 A) {
+    return !c->env.batch_refit && A <= 4096 && K <= 16384 && (M == 1 || M <= plsk::MMAX);
+}
+
+// XX (K x K) summed over the ranks into c->xx: from the upload that formed this member's part, or from X
+template <typename T>
+int batch_xx(pls_hip_context *c, const T *X, i64 ldx, i64 N, int K) {
+    const i64 KK = (i64)K * K;
+    CHK(ensure(c, c->xx, (size_t)KK * 8));
+    if (c->pre_xx) {
+        CHK(ensure(c, c->red2, (size_t)plsk::RED_SLICES * KK * 8));
+        hipLaunchKernelGGL(plsk::fill_slices_kernel, dim3((unsigned)((KK + plsk::WG - 1) / plsk::WG)), dim3(plsk::WG), 0, c->stream,
+                           c->pre_xx, (int)KK, (double *)c->red2.p);
+        LAUNCH_CHECK(c);
+        return compute_xx_finish(c, K, (double *)c->xx.p);
+    }
+    return compute_xx<T>(c, X, ldx, N, K, (double *)c->xx.p);
+}
+
+// red (RED_SLICES slices of K x C, slice stride K * C) = this rank's X^T G, G = C columns (ld ldg)
+template <typename T>
+int batch_xtg(pls_hip_context *c, const T *X, i64 ldx, const T *G, i64 ldg, i64 N, int K, i64 C, double *red) {
+    constexpr int V = plsk::SyrkCfg<T>::V, RB = plsk::SyrkCfg<T>::RB;
+    const i64 KC = (i64)K * C;
+    const bool mfma = ((uintptr_t)X % 16) == 0 && ((uintptr_t)G % 16) == 0 && ldx % V == 0 && ldg % V == 0;
+    if (mfma) {
+        const int nbk = (K + plsk::SYRK_TB - 1) / plsk::SYRK_TB, nbc = (int)((C + plsk::SYRK_TB - 1) / plsk::SYRK_TB);
+        const i64 nblocks = (i64)nbk * nbc, slots = 2 * (i64)c->num_cu, nslabs = (N + RB - 1) / RB;
+        // all workgroups resident at once when the blocks allow it, about eight residency waves otherwise (launch_syrk)
+        i64 S = nblocks <= slots ? slots / nblocks : (8 * slots + nblocks - 1) / nblocks;
+        S = std::max<i64>(1, std::min<i64>(std::min<i64>(S, nslabs), 64));
+        while (S > 1 && S * KC * 8 > ((i64)1 << 30)) --S;
+        if (ensure(c, c->part, (size_t)S * KC * 8) == PLS_HIP_OK &&
+            plsk::raise_dynamic_lds((const void *)plsk::xtg_kernel<T>, (int)plsk::SyrkCfg<T>::LDS_BYTES)) {
+            {
+                Scope s(c, PLS_HIP_FAM_XTY, (i64)N * K * sizeof(T) * nbc + (i64)N * C * sizeof(T) * nbk + S * KC * 8);
+                hipLaunchKernelGGL((plsk::xtg_kernel<T>), dim3((unsigned)nblocks, (unsigned)S), dim3(256), plsk::SyrkCfg<T>::LDS_BYTES,
+                                   c->stream, X, ldx, G, ldg, N, K, (int)C, nbc, 1, (double *)c->part.p, (i64)K, KC);
+                LAUNCH_CHECK(c);
+            }
+            return launch_reduce(c, (const double *)c->part.p, (int)S, (int)KC, nullptr, 0, red);
+        }
+        c->err.clear();
+    }
+    // layouts the matrix-core kernel declines (odd ld, pointers aligned to 8 bytes only): the column-reduction kernel in blocks of
+    // 32 columns, into the same slices -- as compute_xx_local falls back
+    CHK(ensure(c, c->part, (size_t)max_partial_rows(c, N, K) * (size_t)K * BATCH_CB * 8));
+    for (i64 c0 = 0; c0 < C; c0 += BATCH_CB) {
+        const int cb = (int)std::min<i64>(BATCH_CB, C - c0);
+        int nb = 0;
+        CHK(launch_xty<T>(c, X, ldx, G + c0 * ldg, ldg, N, K, cb, (double *)c->part.p, &nb));
+        CHK(launch_reduce(c, (const double *)c->part.p, nb, K * cb, nullptr, 0, red + c0 * K, KC));
+    }
+    return PLS_HIP_OK;
+}
+
+// problems per round of the batched route: as many as 4 GB and half of the free device memory hold (0: not even one)
+i64 batch_round_size(pls_hip_context *c, i64 K, i64 M, i64 A, i64 nprob) {
+    const plsk::BatchLayout L((int)K, (int)M, (int)A);
+    const i64 KP = K + (K & 1);
+    // workspace, V and r columns, the sliced product and the message, and the row-split partial blocks of the product
+    const i64 per = (L.total + 2 * KP + plsk::RED_SLICES * (2 * K + 1) * M + M) * 8 + 16 * K * M * 8;
+    size_t fr = 0, tot = 0;
+    if (hipMemGetInfo(&fr, &tot) != hipSuccess) {
+        (void)hipGetLastError();
+        fr = (size_t)BATCH_ROUND_BYTES;
+    }
+    i64 nb = std::min<i64>(BATCH_ROUND_BYTES, (i64)(fr / 2)) / per;
+    nb = std::min<i64>(nb, ((i64)1 << 30) / std::max<i64>(1, (K + 1) * M));  // K * C and a message slice stay below 2^31 values
+    if (c->env.batch_round > 0) nb = std::min<i64>(nb, c->env.batch_round);
+    return std::max<i64>(0, std::min<i64>(nb, nprob));
+}
+
+// The batched route on device pointers; any of R, Q, tt, B, ssy may be null.  PLS_HIP_ERR_ALLOC: workspace does not fit.
+template <typename T>
+int fit_batch_device(pls_hip_context *c, const T *X, i64 ldx, const T *Ys, i64 ldy, i64 N, int K, int M, int A, i64 nprob,
+                     double *R, double *Q, double *tt, double *B, double *ssy) {
+    const plsk::BatchLayout L(K, M, A);
+    const i64 nround = batch_round_size(c, K, M, A, nprob);
+    if (nround < 1) return fail(c, PLS_HIP_ERR_ALLOC, "fit_batch: the workspace of one problem does not fit");
+    const i64 KP = K + (K & 1), per = (i64)(K + 1) * M;
+    const i64 Cmax = nround * M;
+    const i64 piece = c->reducer ? std::max<i64>(1, BATCH_MSG_CAP / per) : nround;  // whole problems per message
+    CHK(ensure(c, c->bws, (size_t)nround * L.total * 8));
+    CHK(ensure(c, c->bv, (size_t)2 * KP * nround * 8));
+    CHK(ensure(c, c->bred, (size_t)plsk::RED_SLICES * K * Cmax * 8));
+    CHK(ensure(c, c->bmsg, (size_t)plsk::RED_SLICES * per * std::min(piece, nround) * 8));
+    CHK(ensure(c, c->bssy, (size_t)Cmax * 8));
+    CHK(batch_xx<T>(c, X, ldx, N, K));
+    const double *XX = (const double *)c->xx.p;
+    double *ws = (double *)c->bws.p, *Vm = (double *)c->bv.p, *Rc = Vm + KP * nround;
+    double *red = (double *)c->bred.p, *msg = (double *)c->bmsg.p, *sv = (double *)c->bssy.p;
+    if (!plsk::raise_dynamic_lds((const void *)plsk::xtg_kernel<double>, (int)plsk::SyrkCfg<double>::LDS_BYTES))
+        return fail(c, PLS_HIP_ERR_DEVICE, "dynamic LDS limit of the matrix-core product could not be raised");
+    const size_t cs_bytes = (size_t)A * 8;
+    const int nbk = (K + plsk::SYRK_TB - 1) / plsk::SYRK_TB;
+    for (i64 b0 = 0; b0 < nprob; b0 += nround) {
+        const i64 nb = std::min(nround, nprob - b0), C = nb * M, KC = (i64)K * C;
+        const T *G = Ys + b0 * M * ldy;
+        if (N > 0) {
+            CHK(batch_xtg<T>(c, X, ldx, G, ldy, N, K, C, red));
+            hipLaunchKernelGGL((plsk::batch_ssy_kernel<T>), dim3((unsigned)C), dim3(plsk::WG), 0, c->stream, G, ldy, N, sv);
+            LAUNCH_CHECK(c);
+        }
+        for (i64 p0 = 0; p0 < nb; p0 += piece) {
+            const i64 np = std::min(piece, nb - p0), Lm = per * np;
+            if (N > 0) {
+                const unsigned g = (unsigned)std::min<i64>((Lm + plsk::WG - 1) / plsk::WG, 8192);
+                hipLaunchKernelGGL(plsk::batch_pack_kernel, dim3(g), dim3(plsk::WG), 0, c->stream, (const double *)red, KC,
+                                   (const double *)sv, K, M, p0 * M, Lm, msg);
+                LAUNCH_CHECK(c);
+            } else {
+                HIPCHK(c, hipMemsetAsync(msg, 0, (size_t)plsk::RED_SLICES * Lm * 8, c->stream));  // an empty shard
+            }
+            CHK(do_allreduce(c, msg, (i64)plsk::RED_SLICES * Lm));
+            hipLaunchKernelGGL(plsk::batch_step_kernel, dim3((unsigned)np), dim3(plsk::UPD_THREADS), cs_bytes, c->stream,
+                               (const double *)msg, Lm, (const double *)Vm, Rc, KP, ws, (int)p0, K, M, A, -1, (int)c->opt_power_iters);
+            LAUNCH_CHECK(c);
+        }
+        const int nbc = (int)((nb + plsk::SYRK_TB - 1) / plsk::SYRK_TB);
+        for (int a = 0; a < A; ++a) {
+            {   // V = XX [r_0 r_1 ...]: XX is symmetric, so this is the product XX^T Rc of xtg_kernel with one row split
+                Scope s(c, PLS_HIP_FAM_SMALL, ((i64)K * K * nbc + 2 * (i64)K * nb * nbk) * 8);
+                hipLaunchKernelGGL((plsk::xtg_kernel<double>), dim3((unsigned)(nbk * nbc), 1), dim3(256),
+                                   plsk::SyrkCfg<double>::LDS_BYTES, c->stream, XX, (i64)K, (const double *)Rc, KP, (i64)K, K, (int)nb,
+                                   nbc, (K & 1) ? 0 : 1, Vm, KP, (i64)0);
+                LAUNCH_CHECK(c);
+            }
+            Scope s(c, PLS_HIP_FAM_SMALL, nb * ((i64)K * M * 3 + (i64)K * (2 * (a + 2)) + 2 * K) * 8);
+            hipLaunchKernelGGL(plsk::batch_step_kernel, dim3((unsigned)nb), dim3(plsk::UPD_THREADS), cs_bytes, c->stream,
+                               (const double *)nullptr, (i64)0, (const double *)Vm, Rc, KP, ws, 0, K, M, A, a, (int)c->opt_power_iters);
+            LAUNCH_CHECK(c);
+        }
+        if (R || Q || tt || B || ssy) {
+            hipLaunchKernelGGL(plsk::batch_finish_kernel, dim3((unsigned)nb), dim3(plsk::WG), 0, c->stream, (const double *)ws, K, M, A,
+                               b0, R, Q, tt, B, ssy);
+            LAUNCH_CHECK(c);
+        }
+    }
+    return PLS_HIP_OK;
+}
+
+// The per-problem route: one KERNEL_TYPE2 fit per problem under the handle's plan (its own collectives on a sharded handle),
+// tt from the X^T X that fit left in the workspace, ssy from a column sweep (one message of RED_SLICES * M on a sharded handle).
+template <typename T>
+int fit_batch_refit(pls_hip_context *c, const T *X, i64 ldx, const T *Ys, i64 ldy, i64 N, int K, int M, int A, i64 nprob,
+                    double *R, double *Q, double *tt, double *B, double *ssy) {
+    const i64 KA = (i64)K * A, MA = (i64)M * A;
+    CHK(ensure(c, c->bws, (size_t)(3 * KA + MA + M) * 8));
+    CHK(ensure(c, c->bmsg, (size_t)plsk::RED_SLICES * M * 8));
+    double *Wf = (double *)c->bws.p, *Pf = Wf + KA, *Rf = Pf + KA, *Qf = Rf + KA, *sv = Qf + MA;
+    double *msg = (double *)c->bmsg.p;
+    const double *saved_xx = c->pre_xx, *saved_xy = c->pre_xy;  // (X^T Y of an upload belongs to another Y)
+    c->pre_xx = c->pre_xy = nullptr;
+    int rc = PLS_HIP_OK;
+    for (i64 b = 0; b < nprob && rc == PLS_HIP_OK; ++b) {
+        const T *Yb = Ys + b * M * ldy;
+        rc = fit_device<T>(c, X, ldx, Yb, ldy, N, K, M, A, PLS_HIP_KERNEL_TYPE2, Wf, Pf, Qf, Rf, (T *)nullptr, 0,
+                           B ? B + b * K * M : nullptr);
+        if (rc != PLS_HIP_OK) break;
+        if (R && hipMemcpyAsync(R + b * KA, Rf, (size_t)KA * 8, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) rc = PLS_HIP_ERR_DEVICE;
+        if (Q && hipMemcpyAsync(Q + b * MA, Qf, (size_t)MA * 8, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) rc = PLS_HIP_ERR_DEVICE;
+        if (rc != PLS_HIP_OK) { c->err = "fit_batch: copy of a problem's results failed"; break; }
+        if (tt) {
+            hipLaunchKernelGGL(plsk::batch_tt_kernel, dim3((unsigned)A), dim3(plsk::WG), 0, c->stream, (const double *)c->xx.p,
+                               (const double *)Rf, K, tt + b * A);
+            if (hipGetLastError() != hipSuccess) { rc = fail(c, PLS_HIP_ERR_DEVICE, "fit_batch: launch failed"); break; }
+        }
+        if (ssy) {
+            if (N > 0) hipLaunchKernelGGL((plsk::batch_ssy_kernel<T>), dim3((unsigned)M), dim3(plsk::WG), 0, c->stream, Yb, ldy, N, sv);
+            else if (hipMemsetAsync(sv, 0, (size_t)M * 8, c->stream) != hipSuccess) rc = PLS_HIP_ERR_DEVICE;
+            hipLaunchKernelGGL(plsk::fill_slices_kernel, dim3((unsigned)((M + plsk::WG - 1) / plsk::WG)), dim3(plsk::WG), 0, c->stream,
+                               (const double *)sv, M, msg);
+            if (rc != PLS_HIP_OK || hipGetLastError() != hipSuccess) { rc = fail(c, PLS_HIP_ERR_DEVICE, "fit_batch: launch failed"); break; }
+            rc = do_allreduce(c, msg, (i64)plsk::RED_SLICES * M);
+            if (rc != PLS_HIP_OK) break;
+            hipLaunchKernelGGL(plsk::sum_slices_kernel, dim3((unsigned)((M + plsk::WG - 1) / plsk::WG)), dim3(plsk::WG), 0, c->stream,
+                               (const double *)msg, M, ssy + b * M);
+            if (hipGetLastError() != hipSuccess) { rc = fail(c, PLS_HIP_ERR_DEVICE, "fit_batch: launch failed"); break; }
+        }
+    }
+    c->pre_xx = saved_xx;
+    c->pre_xy = saved_xy;
+    return rc;
+}
+
+// pls_hip_fit_batch behind its argument checks
+int fit_batch_impl(pls_hip_context *h, const void *X, i64 ldx, const void *Ys, i64 ldy, i64 N, i64 K, i64 M, i64 A, i64 nprob,
+                   int dtype, int mem, double *R, double *Q, double *tt, double *B, double *ssy) {
+    const size_t es = esize(dtype);
+    const i64 C = nprob * M;
+    const void *dX = X, *dY = Ys;
+    i64 dldx = ldx, dldy = ldy;
+    double *dR = R, *dQ = Q, *dtt = tt, *dB = B, *dssy = ssy;
+    if (mem == PLS_HIP_MEM_HOST) {
+        const i64 n1 = std::max<i64>(N, 1), ldn = n1 + ((-n1) & 3);  // 16-byte columns for either type
+        CHK(ensure(h, h->hX, (size_t)ldn * K * es));
+        CHK(ensure(h, h->bY, (size_t)ldn * C * es));
+        if (R) CHK(ensure(h, h->boR, (size_t)nprob * K * A * 8));
+        if (Q) CHK(ensure(h, h->boQ, (size_t)nprob * M * A * 8));
+        if (tt) CHK(ensure(h, h->bott, (size_t)nprob * A * 8));
+        if (B) CHK(ensure(h, h->boB, (size_t)nprob * K * M * 8));
+        if (ssy) CHK(ensure(h, h->bossy, (size_t)nprob * M * 8));
+        CHK(h2d(h, h->hX.p, ldn, X, ldx, N, K, es));
+        CHK(h2d(h, h->bY.p, ldn, Ys, ldy, N, C, es));
+        dX = h->hX.p; dY = h->bY.p;
+        dldx = dldy = ldn;
+        dR = R ? (double *)h->boR.p : nullptr;
+        dQ = Q ? (double *)h->boQ.p : nullptr;
+        dtt = tt ? (double *)h->bott.p : nullptr;
+        dB = B ? (double *)h->boB.p : nullptr;
+        dssy = ssy ? (double *)h->bossy.p : nullptr;
+    }
+    int rc = PLS_HIP_ERR_ALLOC;
+    const bool batched = batch_covers(h, K, M, A);
+    if (batched) {
+        if (dtype == PLS_HIP_F64)
+            rc = fit_batch_device<double>(h, (const double *)dX, dldx, (const double *)dY, dldy, N, (int)K, (int)M, (int)A, nprob, dR,
+                                          dQ, dtt, dB, dssy);
+        else
+            rc = fit_batch_device<float>(h, (const float *)dX, dldx, (const float *)dY, dldy, N, (int)K, (int)M, (int)A, nprob, dR, dQ,
+                                         dtt, dB, dssy);
+    }
+    // declined, or (single rank: the ranks of a sharded handle must not differ in their route) no room for the batched workspace
+    if (!batched || (rc == PLS_HIP_ERR_ALLOC && !h->reducer)) {
+        h->err.clear();
+        if (M > plsk::LM_MAX || K > 32768)
+            return fail(h, PLS_HIP_ERR_UNSUPPORTED, "fit_batch: the per-problem route is pls_hip_fit's: M <= 1024, K <= 32768");
+        if (dtype == PLS_HIP_F64)
+            rc = fit_batch_refit<double>(h, (const double *)dX, dldx, (const double *)dY, dldy, N, (int)K, (int)M, (int)A, nprob, dR, dQ,
+                                         dtt, dB, dssy);
+        else
+            rc = fit_batch_refit<float>(h, (const float *)dX, dldx, (const float *)dY, dldy, N, (int)K, (int)M, (int)A, nprob, dR, dQ,
+                                        dtt, dB, dssy);
+    }
+    if (rc != PLS_HIP_OK) return rc;
+    if (mem == PLS_HIP_MEM_HOST) {
+        if (R) CHK(d2h(h, R, K * A, dR, K * A, K * A, nprob, 8));
+        if (Q) CHK(d2h(h, Q, M * A, dQ, M * A, M * A, nprob, 8));
+        if (tt) CHK(d2h(h, tt, A, dtt, A, A, nprob, 8));
+        if (B) CHK(d2h(h, B, K * M, dB, K * M, K * M, nprob, 8));
+        if (ssy) CHK(d2h(h, ssy, M, dssy, M, M, nprob, 8));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        CHK(check_diverged(h));
+    }
+    return PLS_HIP_OK;
+}
+
+}  // namespace

@@ -33,6 +33,7 @@
 #include "cv_kernels.hpp"
 #include "validation_kernels.hpp"
 #include "xdiag_kernels.hpp"
+#include "batch_kernels.hpp"
 #include "synth_kernels.hpp"
 #include "host_pipeline.hpp"
 #include "exchange_kernels.hpp"
@@ -82,6 +83,8 @@ int pls_hip_create(pls_hip_handle *out, int device, void *stream) {
         auto on = [](const char *name) { const char *e = getenv(name); return e && atoi(e) != 0; };
         c->env.tiny = !off("PLS_HIP_TINY");
         c->env.cv_refit = on("PLS_HIP_CV_REFIT");
+        c->env.batch_refit = on("PLS_HIP_BATCH_REFIT");
+        if (const char *e = getenv("PLS_HIP_BATCH_ROUND")) c->env.batch_round = atoll(e);
         c->env.tail = !off("PLS_HIP_TAIL");
         {
             const char *e = getenv("PLS_HIP_TAIL");
@@ -107,7 +110,8 @@ int pls_hip_destroy(pls_hip_handle h) {
     DevBuf *bufs[] = {&h->tailcnt, &h->resident, &h->rgflags, &h->zeros, &h->part, &h->sspart, &h->xbpart, &h->wide1, &h->red, &h->red2, &h->xx, &h->xyp, &h->praw, &h->xy, &h->v, &h->cs, &h->coop, &h->lm, &h->gxx, &h->gxy, &h->tab,
                       &h->cvidx, &h->cvx, &h->cvy, &h->cvws, &h->cve, &h->cvtx, &h->cvty, &h->cvtt, &h->cvm, &h->cvkeep, &h->cvred, &h->work, &h->hX, &h->hY,
                       &h->hT, &h->hW, &h->hP, &h->hQ, &h->hR, &h->hB, &h->hIn, &h->hOut, &h->valout, &h->valpart, &h->vale, &h->valacc, &h->valkeys,
-                      &h->valhist, &h->xdS, &h->xdQ, &h->xdPT, &h->xdred, &h->xdtv, &h->xdoQ, &h->xdoT, &h->xdoS, &h->xdsmall};
+                      &h->valhist, &h->xdS, &h->xdQ, &h->xdPT, &h->xdred, &h->xdtv, &h->xdoQ, &h->xdoT, &h->xdoS, &h->xdsmall,
+                      &h->bws, &h->bv, &h->bred, &h->bmsg, &h->bssy, &h->bY, &h->boR, &h->boQ, &h->bott, &h->boB, &h->bossy};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (void *q : h->graveyard) (void)hipFree(q);
@@ -188,6 +192,14 @@ int pls_hip_set_reducer(pls_hip_handle h, pls_hip_allreduce_fn fn, void *user, i
     h->reducer_user = user;
     h->rank = rank;
     h->nranks = nranks;
+    return PLS_HIP_OK;
+}
+
+int pls_hip_get_reducer(pls_hip_handle h, int *installed, int *rank, int *nranks) {
+    CHK(check_handle(h));
+    if (installed) *installed = h->reducer ? 1 : 0;
+    if (rank) *rank = h->rank;
+    if (nranks) *nranks = h->nranks;
     return PLS_HIP_OK;
 }
 
@@ -501,6 +513,7 @@ int pls_hip_sse_by_components(pls_hip_handle h, const void *S, int64_t lds, cons
 }  // extern "C"
 
 #include "plan_cv.hpp"
+#include "plan_batch.hpp"
 
 
 extern "C" {
@@ -589,6 +602,20 @@ int pls_hip_cv_folds(pls_hip_handle h, const void *X, int64_t ldx, const void *Y
     // the index list is host memory of the caller: the copy above must have consumed it before we return
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return PLS_HIP_OK;
+}
+
+int pls_hip_fit_batch(pls_hip_handle h, const void *X, int64_t ldx, const void *Ys, int64_t ldy, int64_t N, int64_t K, int64_t M,
+                      int64_t A, int64_t nprob, int dtype, int mem, double *R, double *Q, double *tt, double *B, double *ssy) {
+    CHK(check_handle(h));
+    if (dtype != PLS_HIP_F64 && dtype != PLS_HIP_F32) return fail(h, PLS_HIP_ERR_INVALID, "bad dtype");
+    if (mem != PLS_HIP_MEM_HOST && mem != PLS_HIP_MEM_DEVICE) return fail(h, PLS_HIP_ERR_INVALID, "bad mem kind");
+    const bool empty_member = (N == 0 && h->nranks > 1);  // an empty shard still takes part in the messages
+    const i64 n1 = std::max<i64>(N, 1);
+    if (N < 0 || (N == 0 && !empty_member) || K < 1 || M < 1 || A < 1 || A > K || nprob < 1 || K > (1 << 30) || M > (1 << 20) ||
+        nprob > (1 << 24) || nprob * M > (1 << 30) || (N > 0 && (!X || !Ys)) || ldx < n1 || ldy < n1)
+        return fail(h, PLS_HIP_ERR_INVALID, "bad fit_batch arguments: need N>=1, 1<=A<=K, M>=1, nprob>=1, ld>=N, X and Ys");
+    CHK(set_device(h));
+    return fit_batch_impl(h, X, ldx, Ys, ldy, N, K, M, A, nprob, dtype, mem, R, Q, tt, B, ssy);
 }
 
 int pls_hip_model_sse(pls_hip_handle h, const void *X, int64_t ldx, const void *Y, int64_t ldy, int64_t N,

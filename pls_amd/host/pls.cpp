@@ -804,6 +804,60 @@ XDiagnostics Model::x_diagnostics(const Mat2D &X_new) const {
 }
 
 // ---------------------------------------------------------------------------------------------
+// response-permutation test (extension): every refit in one batched call (pls_hip_fit_batch)
+// ---------------------------------------------------------------------------------------------
+PermutationTest Model::permutation_test(const Mat2D &X, const Mat2D &Y, const std::vector<Colsz> &perms) const {
+    const Index N = X.rows(), M = Y.cols(), Ai = static_cast<Index>(A);
+    if (Y.rows() != N || N < 1 || M < 1) throw std::invalid_argument("PLS::Model::permutation_test: X and Y differ in their rows");
+    if (X.cols() != R.rows()) throw std::invalid_argument("PLS::Model::permutation_test: column count differs from the model's");
+    const Index nprob = static_cast<Index>(perms.size()) + 1;
+    Mat2D Ys(N, nprob * M);  // problem 0: Y itself
+    for (Index b = 0; b < nprob; ++b) {
+        if (b > 0 && perms[static_cast<size_t>(b - 1)].size() != N)
+            throw std::invalid_argument("PLS::Model::permutation_test: a permutation has the wrong length");
+        for (Index i = 0; i < N; ++i) {
+            const Index src = b == 0 ? i : static_cast<Index>(perms[static_cast<size_t>(b - 1)](i));
+            if (src < 0 || src >= N) throw std::invalid_argument("PLS::Model::permutation_test: a permutation index is out of range");
+            for (Index m = 0; m < M; ++m) Ys(i, b * M + m) = Y(src, m);
+        }
+    }
+    std::vector<float_type> q(static_cast<size_t>(nprob * M * Ai)), tt(static_cast<size_t>(nprob * Ai)), ssy(static_cast<size_t>(nprob * M));
+    {
+        const Ctx ctx = _ctx ? _ctx : current_context();
+        ResidentMatrix dX(ctx), dY(ctx);  // (released after the lock)
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        dX.upload(X);
+        dY.upload(Ys);
+        check(ctx, pls_hip_group_fit_batch(ctx->g, dX.m, dY.m, M, Ai, nullptr, q.data(), tt.data(), nullptr, ssy.data()),
+              "pls_hip_group_fit_batch");
+    }
+    // R^2 Y_c = sum_{a <= c} q_a^2 tt_a / ssy: the scores are orthogonal, so the explained sums of squares add up
+    auto r2 = [&](Index b) {
+        Mat2D out(M, Ai);
+        for (Index m = 0; m < M; ++m) {
+            float_type ess = 0;
+            for (Index a = 0; a < Ai; ++a) {
+                const float_type qa = q[static_cast<size_t>(b * M * Ai + m + a * M)];
+                ess += qa * qa * tt[static_cast<size_t>(b * Ai + a)];
+                out(m, a) = ess / ssy[static_cast<size_t>(b * M + m)];
+            }
+        }
+        return out;
+    };
+    PermutationTest out;
+    out.r2y = r2(0);
+    for (Index b = 1; b < nprob; ++b) out.r2y_perm.push_back(r2(b));
+    out.p = Mat2D(M, Ai);
+    for (Index m = 0; m < M; ++m)
+        for (Index a = 0; a < Ai; ++a) {
+            Index ge = 0;
+            for (const Mat2D &pm : out.r2y_perm) ge += pm(m, a) >= out.r2y(m, a) ? 1 : 0;
+            out.p(m, a) = static_cast<float_type>(1 + ge) / static_cast<float_type>(nprob);
+        }
+    return out;
+}
+
+// ---------------------------------------------------------------------------------------------
 // text output (ref :551-580)
 // ---------------------------------------------------------------------------------------------
 // Same lines as the reference prints (ref :551-562), but the A calls of explained_variance -- A

@@ -89,6 +89,55 @@ def pick_components(probw, ref, alpha: float = 0.1):
     return best
 
 
+
+def r2y_by_components(Q, tt, ssy):
+    """Cumulative R^2 Y of batched fits from the outputs of fit_batch: Q (nprob, M, A), tt (nprob, A), ssy (nprob, M) ->
+    (nprob, M, A) with R2[b, m, c] = sum_{a<=c} Q[b, m, a]^2 tt[b, a] / ssy[b, m] (the explained sum of squares of the
+    orthogonal scores over the total).  Pure array code: numpy arrays or torch tensors, no GPU needed."""
+    if _is_torch(Q):
+        Q = Q if Q.dim() == 3 else Q[None]
+        tt = tt.reshape(Q.shape[0], 1, Q.shape[2])
+        ssy = ssy.reshape(Q.shape[0], Q.shape[1], 1)
+        return torch.cumsum(Q * Q * tt, dim=2) / ssy
+    Q = np.asarray(Q, dtype=np.float64)
+    Q = Q if Q.ndim == 3 else Q[None]
+    tt = np.asarray(tt, dtype=np.float64).reshape(Q.shape[0], 1, Q.shape[2])
+    ssy = np.asarray(ssy, dtype=np.float64).reshape(Q.shape[0], Q.shape[1], 1)
+    return np.cumsum(Q * Q * tt, axis=2) / ssy
+
+
+def permutation_pvalues(r2_real, r2_perm):
+    """(1 + #{b : r2_perm[b] >= r2_real}) / (nperm + 1), elementwise over (M, A): the permutation p-value of every
+    (response, component count) with the real model counted among the permutations.  r2_perm: (nperm, M, A)."""
+    r2_real = np.asarray(r2_real, dtype=np.float64)
+    r2_perm = np.asarray(r2_perm, dtype=np.float64)
+    if r2_perm.ndim == r2_real.ndim:
+        r2_perm = r2_perm[None]
+    return (1.0 + np.sum(r2_perm >= r2_real[None], axis=0)) / (r2_perm.shape[0] + 1.0)
+
+
+_BATCH_OUT = ("R", "Q", "tt", "B", "ssy")
+
+
+def _batch_want(want):
+    want = set(want)
+    bad = want - set(_BATCH_OUT)
+    if bad:
+        raise L.PlsHipError(L.ERR_INVALID, f"fit_batch: unknown output(s) {sorted(bad)}")
+    return want
+
+
+def _batch_shapes(K, M, A, nprob):
+    # logical shapes; every problem's block is column-major (K x A ld K, M x A ld M, K x M ld K) inside a C-ordered stack
+    return {"R": (nprob, A, K), "Q": (nprob, A, M), "tt": (nprob, A), "B": (nprob, M, K), "ssy": (nprob, M)}
+
+
+def _batch_view(name, a):
+    """stack of column-major blocks -> (nprob, rows, cols) views"""
+    if name in ("R", "Q", "B"):
+        return a.permute(0, 2, 1) if _is_torch(a) else a.transpose(0, 2, 1)
+    return a
+
 # ---------------------------------------------------------------------------------------------
 # handle
 # ---------------------------------------------------------------------------------------------
@@ -406,6 +455,95 @@ class Handle:
         L.check(rc, self.h)
         return out
 
+    def fit_batch(self, X, Ys, M: int, A: int, want=("B", "Q", "tt", "ssy")):
+        """Many response sets against one X (pls_hip_fit_batch): Ys is N x (nprob * M), problem b owning columns
+        [b*M, (b+1)*M); every problem is the KERNEL_TYPE2 model of (X, Y_b) on the shared X^T X.  Returns a dict of the
+        outputs `want` names: "R" (nprob, K, A), "Q" (nprob, M, A), "tt" (nprob, A), "B" (nprob, K, M), "ssy" (nprob, M) --
+        torch tensors on the device of X for torch inputs (the call only enqueues), numpy arrays for numpy inputs.
+        W, P and T are not available here: fit one problem with fit_device / fit_host for those.
+        Row-sharded handle: a collective, X and Ys the rank's own rows; every rank receives identical outputs."""
+        want = _batch_want(want)
+        if _is_torch(X):
+            X = as_colmajor(X); Ys = as_colmajor(Ys, X.dtype)
+            N, K = X.shape
+            C = Ys.shape[1]
+            if M < 1 or C % M:
+                raise L.PlsHipError(L.ERR_INVALID, "fit_batch: the columns of Ys are not a multiple of M")
+            nprob = C // M
+            shp = _batch_shapes(K, M, A, nprob)
+            out = {k: torch.empty(shp[k], dtype=torch.float64, device=X.device) for k in _BATCH_OUT if k in want}
+            ptr = lambda k: out[k].data_ptr() if k in out else None
+            rc = self._lib.pls_hip_fit_batch(self.h, X.data_ptr() or None, _ld(X), Ys.data_ptr() or None, _ld(Ys), N, K, M, A,
+                                             nprob, self._dt(X), L.MEM_DEVICE, ptr("R"), ptr("Q"), ptr("tt"), ptr("B"), ptr("ssy"))
+            L.check(rc, self.h)
+            self._last_inputs = (X, Ys)
+            return {k: _batch_view(k, v) for k, v in out.items()}
+        dt = np.float32 if np.asarray(X).dtype == np.float32 else np.float64
+        X = _np_f(X, dt); Ys = _np_f(Ys, dt)
+        N, K = X.shape
+        C = Ys.shape[1]
+        if M < 1 or C % M:
+            raise L.PlsHipError(L.ERR_INVALID, "fit_batch: the columns of Ys are not a multiple of M")
+        nprob = C // M
+        shp = _batch_shapes(K, M, A, nprob)
+        out = {k: np.zeros(shp[k]) for k in _BATCH_OUT if k in want}
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        ptr = lambda k: p(out[k]) if k in out else None
+        rc = self._lib.pls_hip_fit_batch(self.h, p(X), max(N, 1), p(Ys), max(N, 1), N, K, M, A, nprob,
+                                         L.F64 if dt == np.float64 else L.F32, L.MEM_HOST, ptr("R"), ptr("Q"), ptr("tt"), ptr("B"),
+                                         ptr("ssy"))
+        L.check(rc, self.h)
+        return {k: _batch_view(k, v) for k, v in out.items()}
+
+    def permutation_test(self, X, Y, A: int, nperm: int, perms=None, seed: int = 0, max_bytes: int = 1 << 30):
+        """Response-permutation (Y-randomisation) test: problem 0 is Y itself, problem b is Y[perms[b-1]] (rows permuted,
+        the M responses of a row together), all fitted against the same X by fit_batch.  perms: (nperm, N) int64; drawn
+        with numpy.random.default_rng(seed).permutation when not given.  The rows are gathered by the array library where
+        the data lives, in chunks whose Ys stays under max_bytes.  Returns dict(r2y (M, A), r2y_perm (nperm, M, A),
+        p (M, A), perms): cumulative R^2 Y per component count, and p = (1 + #{perm >= real}) / (nperm + 1).
+        A handle with a reducer raises ValueError: a permutation moves rows across ranks -- sharded callers build Ys
+        themselves and call fit_batch."""
+        if self._has_reducer():
+            raise ValueError("permutation_test on a row-sharded handle: a permutation moves rows across ranks; "
+                             "build Ys yourself and call fit_batch")
+        on_dev = _is_torch(X)
+        if on_dev:
+            Y2 = Y if Y.dim() == 2 else Y[:, None]
+        else:
+            dt = np.float32 if np.asarray(X).dtype == np.float32 else np.float64
+            X = _np_f(X, dt); Y2 = _np_f(Y, dt)
+        N, M = Y2.shape
+        if perms is None:
+            rng = np.random.default_rng(seed)
+            perms = np.stack([rng.permutation(N) for _ in range(nperm)]) if nperm else np.zeros((0, N), dtype=np.int64)
+        perms = np.ascontiguousarray(np.asarray(perms, dtype=np.int64)).reshape(-1, N)
+        nperm = perms.shape[0]
+        es = 4 if (Y2.dtype == (torch.float32 if on_dev else np.float32)) else 8
+        chunk = max(1, int(max_bytes) // max(1, N * M * es))
+        r2 = []
+        for b0 in range(0, nperm + 1, chunk):  # problem index 0 = the identity
+            b1 = min(nperm + 1, b0 + chunk)
+            rows = [np.arange(N, dtype=np.int64)] if b0 == 0 else []
+            rows += [perms[b - 1] for b in range(max(b0, 1), b1)]
+            idx = np.concatenate(rows)
+            nb = b1 - b0
+            if on_dev:
+                g = Y2[torch.as_tensor(idx, device=Y2.device)]          # (nb * N, M), problem-major
+                Ys = colmajor_empty(N, nb * M, Y2.dtype, Y2.device)
+                Ys.copy_(g.reshape(nb, N, M).permute(1, 0, 2).reshape(N, nb * M))
+            else:
+                Ys = np.asfortranarray(Y2[idx].reshape(nb, N, M).transpose(1, 0, 2).reshape(N, nb * M))
+            o = self.fit_batch(X, Ys, M, A, want=("Q", "tt", "ssy"))
+            part = r2y_by_components(o["Q"], o["tt"], o["ssy"])
+            r2.append(part.cpu().numpy() if on_dev else part)
+        r2 = np.concatenate(r2, axis=0)
+        return dict(r2y=r2[0], r2y_perm=r2[1:], p=permutation_pvalues(r2[0], r2[1:]), perms=perms)
+
+    def _has_reducer(self) -> bool:
+        on, rank, n = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        L.check(self._lib.pls_hip_get_reducer(self.h, ctypes.byref(on), ctypes.byref(rank), ctypes.byref(n)), self.h)
+        return bool(on.value)
+
     def synth_x(self, row0: int, nrows: int, K: int, seed: int, dtype=None, device=None):
         dtype = dtype or torch.float64
         X = colmajor_empty(nrows, K, dtype, device or f"cuda:{self.device}")
@@ -600,6 +738,20 @@ class Group:
                                                           out.get("Q"), out.get("T2"), out.get("S"), vec("ssx"), vec("sst")))
         return out
 
+    def fit_batch(self, X, Ys, M: int, A: int, want=("B", "Q", "tt", "ssy")):
+        """pls_hip_group_fit_batch on resident X (N x K) and Ys (N x nprob*M): numpy outputs as Handle.fit_batch names them"""
+        want = _batch_want(want)
+        N, K, _ = self.shape(X)
+        C = self.shape(Ys)[1]
+        if M < 1 or C % M:
+            raise L.PlsHipError(L.ERR_INVALID, "fit_batch: the columns of Ys are not a multiple of M")
+        nprob = C // M
+        shp = _batch_shapes(K, M, A, nprob)
+        out = {k: np.zeros(shp[k]) for k in _BATCH_OUT if k in want}
+        ptr = lambda k: out[k].ctypes.data_as(ctypes.c_void_p) if k in out else None
+        self._check(self._lib.pls_hip_group_fit_batch(self.g, X, Ys, M, A, ptr("R"), ptr("Q"), ptr("tt"), ptr("B"), ptr("ssy")))
+        return {k: _batch_view(k, v) for k, v in out.items()}
+
     def cv_folds(self, X, Y, A: int, test_idx):
         idx = np.ascontiguousarray(np.asarray(test_idx, dtype=np.int64))
         if idx.ndim == 1:
@@ -780,6 +932,11 @@ class Model:
         out = self.handle.x_diagnostics(X, R, P, tvar=tv, want=("Q", "T2", "ssx"))
         ssx = out["ssx"]
         return dict(Q=out["Q"], T2=out["T2"], R2X=1.0 - ssx[1:] / ssx[0])
+
+    def permutation_test(self, nperm: int, perms=None, seed: int = 0, max_bytes: int = 1 << 30):
+        """Handle.permutation_test on the model's own training data with the model's number of components: is the R^2 Y
+        of this model better than what the same X explains of row-permuted responses?"""
+        return self.handle.permutation_test(self._X, self._Y, self.A, nperm, perms=perms, seed=seed, max_bytes=max_bytes)
 
     def explained_variance_by_components(self, X, Y):
         """(EV, SSE), each M x A: what print_explained_variance (src/pls.cpp:551-562) reports for
