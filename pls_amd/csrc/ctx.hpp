@@ -90,7 +90,11 @@ struct pls_hip_context {
     //   PLS_HIP_BATCH_ROUND=n    at most n problems per round of pls_hip_fit_batch's batched route (tests: several rounds)
     //   PLS_HIP_RESIDENT=0       mid-size single-response fits on the general plan instead of the one-launch resident fit
     //   PLS_HIP_REPLICA_GUARD=0  no replica-divergence check after a sharded fit (must be the same on every rank)
+    //   PLS_HIP_TURNAROUND=0     every fused pass walks ascending with the nt policy throughout (A/B measurements; must be the
+    //                            same on every rank)
     struct Env {
+        bool turnaround = true;
+        i64 turn_edge_bytes = plsk::TURN_EDGE_BYTES;  // (testing build: PLS_HIP_TEST_TURN_EDGE_BYTES)
         bool batch_refit = false;
         i64 batch_round = 0;
         bool tiny = true, cv_refit = false, tail = true, replica_guard = true, resident = true;

@@ -22,6 +22,8 @@
 // The column set of a lane belongs to exactly one wave, so the final X^T t partial needs only
 // an in-wave butterfly -- no atomics anywhere, results are bit-reproducible.
 #pragma once
+#include <type_traits>
+
 #include "common.hpp"
 #include "exchange_kernels.hpp"  // XchgPeers: the push of a sharded fit's sums rides in the tail of the pass
 #include "update_m1.hpp"         // the one-response component update: the last act of the tail
@@ -139,7 +141,27 @@ struct TailUpdate {
 struct WalkWeights {
     int nfull = -1;     // rounds dealt to all workgroups; -1: plain cyclic walk
     unsigned mask = 0;  // bit c: the workgroups with blockIdx % 8 == c also share the tiles behind those rounds
+    // the turn-around (fused_pass_kernel, "direction and edges"):
+    int rev = 0;   // position q of the walk is tile ntiles - 1 - q
+    int edge = 0;  // positions of the leading and of the trailing edge (0: none, ntiles: the sweep is all edge)
 };
+
+// What a launcher is told about the turn-around: sweep a + 1 of a fit walks against sweep a, and the first / last
+// edge_bytes of a sweep take the cache policy that hands them from one sweep to the next inside the Infinity Cache.
+struct Turn {
+    bool on = false;     // false: ascending, nt throughout (PLS_HIP_TURNAROUND=0)
+    bool rev = false;    // this sweep descends
+    i64 edge_bytes = 0;  // S
+};
+
+#ifdef PLS_HIP_TESTING
+// testing/libpls_hip.so only: what the launcher handed the last STORING deflating pass (pls_hip_test_last_turn), so that a
+// test can see that a sweep really had a leading edge, a bulk and a trailing edge
+struct TurnRecord {
+    int rev = 0, edge = 0, ntiles = 0, grid = 0;
+};
+inline TurnRecord g_test_turn;
+#endif
 
 struct SliceTail {
     unsigned *cnt = nullptr;  // nullptr: no tail (reduce_partials_kernel follows the launch)
@@ -365,9 +387,15 @@ __device__ __forceinline__ void slice_tail(const SliceTail &st, const double *pa
 // no address registers.  Lanes whose rows lie beyond N use an offset past num_records.
 // X is streamed exactly once per pass and is far larger than the 256 MiB Infinity Cache: its
 // loads and stores carry the nt (streaming) policy so they do not evict the small reused vectors
-// (scores, partials).  Measured on config 3: read-only pass 0.80 -> 0.71 ms (6.05 TB/s),
+// (scores, partials) -- except at the two ends of an in-place deflating sweep, which the next
+// sweep, walking the other way, finds in that cache (kernel comment, "direction and edges").  Measured on config 3: read-only pass 0.80 -> 0.71 ms (6.05 TB/s),
 // read+write pass 1.81 -> 1.70 ms (profiles/r1/tune_fused_cache_policy.txt).
 constexpr int AUX_NT = 2;
+// The turn-around's edge S: bytes at either end of a sweep that are kept in the 256 MiB Infinity Cache for the next sweep,
+// which walks the other way, and the store policy of the leading edge (lines that are resident and dirty when they are
+// overwritten).  Both from pls_amd/csrc/tune/turnaround_probe.hip: profiles/turnaround/probe.txt.
+constexpr i64 TURN_EDGE_BYTES = 192ll << 20;
+constexpr bool TURN_LEAD_ST_DEFAULT = true;
 
 // Which tiles a workgroup visits.  Cyclic: blockIdx.x, blockIdx.x + gridDim.x, ...  XCD-contiguous (EDGE = 2, below):
 // workgroup b runs on XCD b % 8 under round-robin dispatch; every XCD takes one contiguous eighth of the tiles and its
@@ -423,7 +451,8 @@ struct TileWalk<true, R> {
 // STORE = false (DEFL only): the LAST deflating pass of a fit -- X_{A-1} is read by no later launch, so the tile is deflated in
 // registers (the same FMA, the same rounding to T: scores and loadings come from the same bits) and goes nowhere: no
 // destination descriptor, no stores, no pacing (that exists for the read/write mix only); dst is not touched.  Grid, tile
-// walk and XCD weights are those of the storing pass, so every workgroup sums the same tiles in the same order.
+// walk (with its direction) and XCD weights are those of the storing pass, so every workgroup sums the same tiles in the same
+// order.  It has no edge of its own -- nothing reads X behind it -- and its nt loads still hit what the pass before left.
 template <typename T, int V, int R, int NT, int CPT, bool DEFL, int LDAUX_ = AUX_NT, int STAUX = AUX_NT, bool RDST = false,
           int EDGE = 0, bool TILED = false, bool ONEWG = false, bool STORE = true>
 __global__ __launch_bounds__(NT, (NT / 256) * ((CPT <= 16 && !DEFL && !ONEWG) ? 2 : 1)) void fused_pass_kernel(
@@ -516,160 +545,52 @@ __global__ __launch_bounds__(NT, (NT / 256) * ((CPT <= 16 && !DEFL && !ONEWG) ? 
     const i64 wswitch = (WEIGHTED && wk.nfull >= 0) ? (i64)wk.nfull * gridDim.x : (i64)1 << 62;
     i64 wstep = walk.step();
     bool wshared = true;
-    for (i64 tile = walk.first(); tile * R < walk.nlim(N); buf ^= 1) {
-        const i64 i0 = tile * R + (i64)rp * V;
-        const bool rowok = (i0 < N);  // N % V == 0 (launcher): a pack is all-valid or all-invalid
-        const uint32_t xo = rowok ? xoff : OOR, dof = rowok ? doff : OOR;
-        // LDS operands (v, p_prev) are re-read every tile: an index the compiler cannot prove
-        // loop-invariant keeps 2*CPT fp64 values out of the register file
-        int cgz = cg;
-        asm volatile("" : "+v"(cgz));
-        if constexpr (TILED && DEFL && STORE) {
-            // pacing: `rdst` x 64 cycles of s_sleep before a tile's loads go out (launcher)
-            if (!LATE_FILL || !first_tile)  // (nothing is in flight before the first tile)
-                for (int q = 0; q < pace; ++q) __builtin_amdgcn_s_sleep(1);
-        }
-        Pack<T, V> x[CPT];
-        constexpr int GSTEP = CG * R * (int)sizeof(T);  // TILED: bytes between the column groups of a tile
-        const int trec = K * R * (int)sizeof(T);        // TILED: bytes of a tile
-        if constexpr (TILED) {
-            const __amdgpu_buffer_rsrc_t rs =
-                __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(X + tile * tsx), (short)0, trec, BUF_WORD3);
-#pragma unroll
-            for (int j = 0; j < CPT; ++j) x[j] = buf_ld_so<T, V, LDAUX>(rs, xo, j * GSTEP);
-            __builtin_amdgcn_sched_barrier(0);  // all CPT loads in flight before anything consumes the first
-            if constexpr (LATE_OK) {
-                if (LATE_FILL && first_tile) {  // (uniform)
-                    first_tile = false;
-                    if (tid < CG * CPT) {
-                        vs[tid] = v_late;
-                        ps[tid] = p_late;
-                    }
-                    __syncthreads();
-                }
+    // Direction and edges (deflating passes).  Consecutive sweeps of a fit walk in opposite directions (wk.rev: position q
+    // is tile ntiles - 1 - q; the weighted walk and its switch point work on positions), so the first wk.edge positions of
+    // a sweep -- the leading edge -- are the tiles the sweep before it touched last, and its last wk.edge positions -- the
+    // trailing edge -- the ones the next sweep starts with.  On the tiled copy the edges drop the nt policy where that lets
+    // the Infinity Cache hand the tiles over: both edges load and store with the default policy -- the trailing edge to
+    // allocate there (with nt loads in front of its default-policy stores it hands over less than half as much), the
+    // leading edge to be served on-die and to overwrite the lines where they are; the bulk between them streams (nt) and
+    // leaves them alone.  Measured with pls_amd/csrc/tune/turnaround_probe.hip (profiles/turnaround/probe.txt).  The policy is an immediate of the buffer
+    // instruction, so the loop body (fused_pass_tile.inc) exists once per policy pair and a wave-uniform branch picks the
+    // copy: with the branch around the loads and the stores alone, the operand reads of the deflation were hoisted above
+    // it (+35 VGPRs in the headline kernel, profiles/turnaround/resources.txt).
+    // (the read-only instantiations keep the ascending walk and one policy: they sit exactly at their 128 registers; the
+    // last, non-storing pass of a fit turns around but has no edge of its own -- nothing reads X behind it)
+    constexpr bool TURNS = DEFL;
+    constexpr bool EDGES = TILED && DEFL && STORE;
+    const bool rev = TURNS && wk.rev;
+    const i64 ntl = (N + R - 1) / R;
+    const i64 etrail = ntl - wk.edge;
+    for (i64 pos = walk.first(); pos * R < walk.nlim(N); buf ^= 1) {
+        const i64 tile = rev ? ntl - 1 - pos : pos;
+        // (the body of the loop -- loads, deflation + stores, score, loading partials: fused_pass_tile.inc)
+        if constexpr (EDGES) {
+            if (pos < wk.edge) {  // (uniform) leading edge
+                constexpr int LA = 0, SA = TURN_LEAD_ST_DEFAULT ? 0 : STAUX;
+#include "fused_pass_tile.inc"
+            } else if (pos >= etrail) {  // trailing edge
+                constexpr int LA = 0, SA = 0;
+#include "fused_pass_tile.inc"
+            } else {
+                constexpr int LA = LDAUX, SA = STAUX;
+#include "fused_pass_tile.inc"
             }
         } else {
-#pragma unroll
-            for (int j = 0; j < CPT; ++j) {
-                const int cols = min(CGD, K - CG * j - cgw);  // columns of this group that exist (may be <= 0)
-                const uint32_t nrec = cols > 0 ? (uint32_t)((i64)cols * ldx * (i64)sizeof(T)) : 0u;
-                const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-                    const_cast<T *>(X + tile * tsx + (i64)(j * CG + cgw) * ldx), (short)0, (int)nrec, BUF_WORD3);
-                x[j] = buf_ld<T, V, LDAUX>(rs, xo);
-                __builtin_amdgcn_sched_barrier(0);  // build one descriptor, issue its load, repeat
-            }
+            constexpr int LA = LDAUX, SA = STAUX;
+#include "fused_pass_tile.inc"
         }
-        if (DEFL) {
-            double tp[V];
-            {
-                // t_prev of the lane's rows; behind row NV (padded sweeps) zeros.  Two forms, chosen per instantiation by
-                // measurement (same box, A/B): through a range-checked buffer descriptor -- the headline shape: 701 vs 693
-                // components/s at config 3 -- or as a plain 16-byte load with an element-wise branch for the one straddling
-                // pack -- every other shape: +0.3 ... +0.7 % (config 4, the shards of configs 3 and 5).
-                Pack<T, V> tpk;
-                if constexpr (TBUF) {
-                    tpk = buf_ld<T, V>(rs_tin, rowok ? (uint32_t)(i0 * (i64)sizeof(T)) : OOR);
-                } else if (rowok && i0 + V <= NV) {
-                    tpk = ld_pack_u<T, V>(tprev + i0);
-                } else {  // (rows the sweep does not cover must contribute nothing: the tail kernel owns row NV - 1 of an odd matrix)
-#pragma unroll
-                    for (int e = 0; e < V; ++e) tpk.v[e] = (rowok && i0 + e < NV) ? tprev[i0 + e] : (T)0;
-                }
-#pragma unroll
-                for (int e = 0; e < V; ++e) tp[e] = -(double)tpk.v[e];
-            }
-#pragma unroll
-            for (int j = 0; j < CPT; ++j) {
-                const double pk = ps[cgz + CG * j];
-#pragma unroll
-                for (int e = 0; e < V; ++e) x[j].v[e] = (T)fma(tp[e], pk, (double)x[j].v[e]);
-                if constexpr (!STORE) {
-                    continue;  // the deflated tile lives in registers only
-                } else if constexpr (TILED) {
-                    const __amdgpu_buffer_rsrc_t rd =
-                        __builtin_amdgcn_make_buffer_rsrc(dst + tile * tsd, (short)0, trec, BUF_WORD3);
-                    // (write-through stores -- sc1 | nt, sc0 | sc1 | nt: nothing dirty in L2 when the launch ends -- measured in
-                    // round 5: the pass +2.5 us on a shard, +23 us at config 3, the boundary behind it no shorter)
-                    buf_st_so<T, V, STAUX>(rd, dof, j * GSTEP, x[j]);
-                } else if constexpr (RDST) {  // lane offsets span several destination tiles: columns >= K masked per lane
-                    const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(
-                        dst + tile * dtile + (i64)j * CG * ldd, (short)0, 0x7fffffff, BUF_WORD3);
-                    buf_st<T, V, STAUX>(rd, (cg + CG * j < K) ? dof : OOR, x[j]);
-                } else {
-                    const int cols = min(CG, K - CG * j);
-                    const uint32_t nrec = cols > 0 ? (uint32_t)((i64)cols * ldd * (i64)sizeof(T)) : 0u;
-                    const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(
-                        dst + tile * tsd + (i64)j * CG * ldd, (short)0, (int)nrec, BUF_WORD3);
-                    buf_st<T, V, STAUX>(rd, dof, x[j]);
-                }
-            }
-        }
-        // the deflated tile goes out BEFORE the score arithmetic (left to itself the compiler sinks the stores behind the
-        // score FMAs and the first butterfly level: 1.387 instead of 1.354 ms per launch at config 3)
-        if constexpr (DEFL && STORE) __builtin_amdgcn_sched_barrier(0);
-        // score: partial over this lane's columns, then over the lanes / waves sharing the rows
-        double tp2[V];
-#pragma unroll
-        for (int e = 0; e < V; ++e) tp2[e] = 0.0;
-#pragma unroll
-        for (int j = 0; j < CPT; ++j) {
-            const double vk = vs[cgz + CG * j];
-#pragma unroll
-            for (int e = 0; e < V; ++e) tp2[e] = fma((double)x[j].v[e], vk, tp2[e]);
-        }
-#pragma unroll
-        for (int e = 0; e < V; ++e)
-            tp2[e] = xor_range_sum<RP, WAVE>(tp2[e]);
-        if (lane < RP)
-#pragma unroll
-            for (int e = 0; e < V; ++e) tred[buf][wv][rp * V + e] = tp2[e];
-        __syncthreads();
-        double t[V];
-#pragma unroll
-        for (int e = 0; e < V; ++e) {
-            double s = 0.0;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) s += tred[buf][w][rp * V + e];
-            t[e] = (double)(T)s;  // the score as stored
-        }
-        if (cg == 0 && rowok) {
-            Pack<T, V> o;
-#pragma unroll
-            for (int e = 0; e < V; ++e) o.v[e] = (T)t[e];
-            if (i0 + V <= NV) {
-                st_pack_u<T, V>(tout + i0, o);
-            } else {  // the pack that straddles the last valid row (padded sweeps only)
-#pragma unroll
-                for (int e = 0; e < V; ++e)
-                    if (i0 + e < NV) tout[i0 + e] = o.v[e];
-            }
-#pragma unroll
-            for (int e = 0; e < V; ++e) ss = fma(t[e], t[e], ss);
-        }
-        // loading: p_raw[k] += sum over the lane's rows of x[i,k] * t[i]   (rows >= N hold x = 0)
-        // fp32 storage: the tile is converted to fp64 again here -- the empty asm hides the stored values from
-        // common-subexpression elimination, which would otherwise keep the fp64 copies of the whole tile made for
-        // the score alive across the barrier (2x the registers of the tile: 135-217 spilled VGPRs, 2.3 TB/s)
-        if (sizeof(T) < sizeof(double)) {
-#pragma unroll
-            for (int j = 0; j < CPT; ++j)
-#pragma unroll
-                for (int e = 0; e < V; ++e) asm volatile("" : "+v"(x[j].v[e]));
-        }
-#pragma unroll
-        for (int j = 0; j < CPT; ++j)
-#pragma unroll
-            for (int e = 0; e < V; ++e) pacc[j] = fma((double)x[j].v[e], t[e], pacc[j]);
         if constexpr (!WEIGHTED) {
-            tile += walk.step();
+            pos += walk.step();
             continue;
         }
-        tile += wstep;
-        if (wshared && tile >= wswitch) {  // (uniform) the shared rounds are over
+        pos += wstep;
+        if (wshared && pos >= wswitch) {  // (uniform) the shared rounds are over
             if (!wfast) break;
             wshared = false;
             const int nfc = __builtin_popcount(wk.mask), below = __builtin_popcount(wk.mask & ((1u << (blockIdx.x & 7)) - 1u));
-            tile = wswitch + (i64)(blockIdx.x >> 3) * nfc + below;
+            pos = wswitch + (i64)(blockIdx.x >> 3) * nfc + below;
             wstep = (i64)(gridDim.x >> 3) * nfc;
         }
     }
@@ -1392,7 +1313,8 @@ int launch_fused_pass(hipStream_t stream, int num_cu, const T *X, i64 ldx, i64 t
                       i64 N, int K, const double *v, const T *tprev, const double *pprev, T *tout,
                       double *part, int max_rows, double *sspart, int *nb, int *nss, int grid_hint, int rdst = 0,
                       bool src_padded = false, const SliceTail *tail = nullptr, bool *tail_used = nullptr,
-                      bool *upd_done = nullptr, bool store = true) {
+                      bool *upd_done = nullptr, bool store = true, const Turn &turn = Turn()) {
+    // turn: direction of this sweep and the bytes of its edges (kernel comment, "direction and edges")
     // *upd_done: the tail ran the component update as well (tail->upd set by the caller and the shape has room for it)
     // tail (cnt, red, npush, seq, peers set by the caller): sum the partial rows inside the launch (slice_tail) when the
     // grid is large enough; *tail_used tells the caller whether reduce_partials_kernel is still to run
@@ -1498,6 +1420,17 @@ int launch_fused_pass(hipStream_t stream, int num_cu, const T *X, i64 ldx, i64 t
         }
         // (the one-descriptor form for READ-ONLY passes over the copy was built in round 5: 52 bytes of scratch per lane instead
         // of 24 -- the 128-register shape's spills are its 64 tile + 32 accumulator registers, not its descriptors)
+        if (turn.on && defl) {  // (kernel comment, "direction and edges")
+            wk.rev = turn.rev ? 1 : 0;
+            if (tiled) {  // whole rounds of the grid; a sweep of fewer than two edges is all edge
+                const i64 round_bytes = grid * (i64)R * K * (i64)sizeof(T);
+                const i64 epos = turn.edge_bytes / round_bytes * grid;
+                wk.edge = (int)(2 * epos >= ntiles ? ntiles : epos);
+            }
+        }
+#ifdef PLS_HIP_TESTING
+        if (stores) g_test_turn = TurnRecord{wk.rev, wk.edge, (int)ntiles, (int)grid};
+#endif
         if (CGX > 32 && defl && !tiled) return 1;
 #define FUSED_LAUNCH(CPT_, DEFL_, EDGE_, TILED_, STORE_, dyn_)                                                            \
     do {                                                                                                                  \

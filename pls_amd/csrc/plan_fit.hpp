@@ -530,6 +530,10 @@ int fit_device(pls_hip_context *c, const T *X, i64 ldx, const T *Y, i64 ldy, i64
         // loading launch behind launch_deflate_score reads what that stored: the store is not dead), not on the unfused plan;
         // the deferred plan has always skipped its last store.
         const bool store_x = (a + 1 < A);  // X_a goes back to memory (false: it lives in the pass's registers only)
+        // The turn-around: even components descend, odd ones ascend -- a function of the component index alone, so a fit
+        // computes the same bits whatever ran before it on the handle and every rank of a sharded fit walks alike.  Only
+        // deflating passes turn (the launcher ignores it for a read-only pass): components 0 and 1 ascend, 2 is the first to descend.
+        const plsk::Turn turn{c->env.turnaround, c->env.turnaround && a % 2 == 0, c->env.turn_edge_bytes};
         const bool want_upd = tail.cnt && (c->env.tail_update == 2 || (c->env.tail_update == 1 && !defl_pass)) && M == 1 &&
                               K <= plsk::UPD1_KMAX && update_is_single(K, M, A, a) && (!c->reducer || want_push);
         tail.npush = 0;
@@ -595,11 +599,11 @@ int fit_device(pls_hip_context *c, const T *X, i64 ldx, const T *Y, i64 ldy, i64
                     if (mid_cg && a >= 2)  // half-height tiles of the working copy, in place
                         rc = plsk::launch_fused_pass<T, 64>(c->stream, c->num_cu, work, ldw, tsw, work, ldw, tsw, N, K, v,
                                                             tprev, pprev, Tm + (i64)a * ldt, part, (int)prow, sspart,
-                                                            &nb, &nss, (int)c->opt_fused_grid, 0, true, &tail, &tail_used, &upd_done, store_x);
+                                                            &nb, &nss, (int)c->opt_fused_grid, 0, true, &tail, &tail_used, &upd_done, store_x, turn);
                     else {  // (a == 1 with mid_cg: X in 256-byte segments -> half-height tiles; A = 2: nothing is stored, no tile shape)
 #define TALL_PASS(CG_) plsk::launch_fused_pass<T, CG_>(c->stream, c->num_cu, Xc, ldc, tsc, (tprev && store_x) ? work : nullptr, ldw, tsw, N, K, v, tprev, \
                                                        pprev, Tm + (i64)a * ldt, part, (int)prow, sspart, &nb, &nss,                        \
-                                                       (int)c->opt_fused_grid, (mid_cg && tprev && store_x) ? (int)WR : 0, Xc == work, &tail, &tail_used, &upd_done, store_x)
+                                                       (int)c->opt_fused_grid, (mid_cg && tprev && store_x) ? (int)WR : 0, Xc == work, &tail, &tail_used, &upd_done, store_x, turn)
                         rc = tall_cg == 8 ? TALL_PASS(8) : (tall_cg == 16 ? TALL_PASS(16) : TALL_PASS(32));
 #undef TALL_PASS
                     }
@@ -631,7 +635,7 @@ int fit_device(pls_hip_context *c, const T *X, i64 ldx, const T *Y, i64 ldy, i64
                     Scope s(c, PLS_HIP_FAM_FUSED, bytes);
 #define WIDE_PASS(CG_) plsk::launch_fused_pass<T, CG_>(c->stream, c->num_cu, work, ldw, tsw, work, ldw, tsw, N, K, v, tprev, pprev, \
                                                         Tm + (i64)a * ldt, part, (int)prow, sspart, &nb, &nss, (int)c->opt_fused_grid, 0, true, \
-                                                        &tail, &tail_used, &upd_done, store_x)
+                                                        &tail, &tail_used, &upd_done, store_x, turn)
                     rc = wide_cg == 8 ? WIDE_PASS(8) : (wide_cg == 16 ? WIDE_PASS(16) : (wide_cg == 32 ? WIDE_PASS(32)
                          : (wide_cg == 64 ? WIDE_PASS(64) : (wide_cg == 128 ? WIDE_PASS(128) : (wide_cg == 256 ? WIDE_PASS(256) : WIDE_PASS(512))))));
 #undef WIDE_PASS

@@ -63,6 +63,12 @@ __attribute__((visibility("default"))) int pls_hip_test_set_pass_stamps(void *bu
     unsigned long long *p = (unsigned long long *)buf;
     return hipMemcpyToSymbol(HIP_SYMBOL(plsk::g_pass_stamps), &p, sizeof(p)) == hipSuccess ? 0 : 1;
 }
+// out[4] = {descending, positions per edge, tiles, grid} of the last storing deflating pass that was launched
+__attribute__((visibility("default"))) int pls_hip_test_last_turn(int *out) {
+    if (!out) return 1;
+    out[0] = plsk::g_test_turn.rev; out[1] = plsk::g_test_turn.edge; out[2] = plsk::g_test_turn.ntiles; out[3] = plsk::g_test_turn.grid;
+    return 0;
+}
 #endif
 
 int pls_hip_create(pls_hip_handle *out, int device, void *stream) {
@@ -92,6 +98,10 @@ int pls_hip_create(pls_hip_handle *out, int device, void *stream) {
         }
         c->env.replica_guard = !off("PLS_HIP_REPLICA_GUARD");
         c->env.resident = !off("PLS_HIP_RESIDENT");
+        c->env.turnaround = !off("PLS_HIP_TURNAROUND");
+#ifdef PLS_HIP_TESTING
+        if (const char *e = getenv("PLS_HIP_TEST_TURN_EDGE_BYTES")) c->env.turn_edge_bytes = atoll(e);  // (small matrices with a bulk, tests only)
+#endif
         if (const char *e = getenv("PLS_HIP_XB4")) c->env.xb4 = atoi(e);
         if (const char *e = getenv("PLS_HIP_RESIDENT_GRAM")) c->env.resident_gram = atoi(e);
     }
