@@ -80,12 +80,25 @@ typedef enum { PLS_HIP_MEM_HOST = 0, PLS_HIP_MEM_DEVICE = 1 } pls_hip_mem;
  *           K x K data as KERNEL_TYPE2 does (tt = r^T XX r, p = XX r / tt, src/pls.cpp:422-425), then
  *           T = X R in one pass.  2 + A*0 passes over X; pays off when A exceeds ~K/50.
  *  AUTO   : KERNEL or GRAM, whichever a bandwidth / matrix-core cost model predicts to be faster for
- *           the shape of the call (GRAM only for K <= 2048, single rank). */
+ *           the shape of the call (GRAM only for K <= 2048, single rank).  AUTO never picks DUAL.
+ *  DUAL   : the sample-space plan for short, wide X (hundreds to a few thousand rows, any number of columns): G = X X^T
+ *           (N x N) once on the matrix cores, the component loop on N-sized data only -- the scores are mutually
+ *           orthogonal, so XY_a = X^T (Y - T_a Q_a^T) and everything :403-429 needs is a product with G -- then W and P
+ *           from ONE product X^T [U | T diag(1/tt)] (one sweep per 64 columns of [U | T], i.e. one up to A = 32).  Two
+ *           sweeps over X whatever A is, no K x K object, no limit on K.  Opt-in, PLS_HIP_KERNEL_TYPE1 only
+ *           (PLS_HIP_KERNEL_TYPE2 ignores it as it ignores every plan).  Limits, refused with PLS_HIP_ERR_UNSUPPORTED
+ *           before anything is written: N <= 8192 (G is N x N doubles: 512 MB there), M <= 32, no reducer / a group of
+ *           one member (G needs every row).  For M > 1 the sign of a component may differ from the other plans' (the
+ *           eigenvector is normalised in the response space from a differently rounded matrix); B does not depend on
+ *           it.  PLS_HIP_OPT_FUSE, _DEFER and _WORK_LAYOUT do not apply; a DUAL fit is never captured by
+ *           PLS_HIP_OPT_GRAPH, it simply runs.  Like GRAM it squares the singular values of X; unlike GRAM it
+ *           orthogonalises every score against the earlier ones explicitly. */
 typedef enum {
     PLS_HIP_ALGO_KERNEL = 0,
     PLS_HIP_ALGO_NIPALS = 1,
     PLS_HIP_ALGO_GRAM = 2,
-    PLS_HIP_ALGO_AUTO = 3
+    PLS_HIP_ALGO_AUTO = 3,
+    PLS_HIP_ALGO_DUAL = 4
 } pls_hip_algo;
 
 typedef enum {
@@ -204,6 +217,9 @@ PLS_HIP_API int pls_hip_get_timing(pls_hip_handle h, pls_hip_timing *out);
  * update runs from global memory: correct, about a millisecond per component slower).  Single-response problems that fit
  * one workgroup's registers (N <= 1024, K <= 26 * floor(16 / ceil(N/64))) run as ONE launch under the KERNEL / AUTO plans.
  * A > rank(X) yields inf/NaN in the surplus columns, as in the reference (:427-428).
+ * Under PLS_HIP_ALGO_DUAL (PLS_HIP_KERNEL_TYPE1): the same outputs from G = X X^T in two sweeps over X, any K, any
+ * ld >= N, element-aligned pointers, either storage type, either memory kind; N > 8192, M > 32 or a handle with a reducer
+ * return PLS_HIP_ERR_UNSUPPORTED with every output untouched.  Workspace: N^2 doubles for G, up to 4 GB of split partials.
  */
 PLS_HIP_API int pls_hip_fit(pls_hip_handle h, const void *X, int64_t ldx, const void *Y, int64_t ldy,
                 int64_t N, int64_t K, int64_t M, int64_t A, int method, int dtype, int mem,

@@ -34,6 +34,7 @@ struct pls_hip_context {
     DevBuf valout, valpart, vale, valacc, valkeys, valhist;  // pls_hip_validation (plan_validation.hpp)
     DevBuf xdS, xdQ, xdPT, xdred, xdtv, xdoQ, xdoT, xdoS, xdsmall;  // pls_hip_x_diagnostics (plan_xdiag.hpp): scores, column-block sums, the message, tvar, host staging
     DevBuf bws, bv, bred, bmsg, bssy, bY, boR, boQ, bott, boB, bossy;  // pls_hip_fit_batch (plan_batch.hpp): per-problem workspace, V and r columns, the sliced product, the message, host staging
+    DevBuf dG, dpart, dV, dT, dY, dZ, dC, dscr;  // PLS_HIP_ALGO_DUAL (plan_dual.hpp): X X^T, its split partials, [U | T / tt], the fp64 scores, Y_a, G Y_a, C, small vectors
     i64 opt_val_lds_rows = -1;  // PLS_HIP_OPT_VALIDATION_LDS_ROWS; -1 = the device's own limit
     i64 val_lds_rows_dev = -1;  // that limit, found on first use
     std::string err;

@@ -1,0 +1,330 @@
+// dual_kernels.hpp -- the kernels of the sample-space plan (PLS_HIP_ALGO_DUAL, plan_dual.hpp): a fit of a short, wide X from
+// G = X X^T (N x N) instead of from X^T X (K x K).
+//
+//   xxt_kernel            G = X X^T on v_mfma_f64_16x16x4_f64, the blocks on or above the diagonal, the sum over the columns of
+//                         X split over workgroups; xxt_reduce_kernel adds the partial blocks in split order and mirrors them
+//   dual_gy_kernel        Z = G Y_a (N x M): one wave per column of the symmetric G, the whole chip
+//   dual_step_kernel      everything else of a component, N (M + a) work, ONE workgroup: direction, norm, orthogonalisation
+//                         of the score against the earlier ones, loading of Y, deflation of Y_a
+//   dual_xtv_kernel       [W | P] = X^T [U | T diag(1/tt)], up to 64 columns per sweep over X, on the matrix cores
+//   dual_r_kernel         r_a = w_a - sum_{j<a} C[j, a] r_j, a thread per row of R
+//   dual_convert_kernel   Y -> fp64 working copy, fp64 scores -> T in the storage type
+//
+// v_mfma_f64_16x16x4_f64: lane l holds A[row l & 15][k = l >> 4], B[k = l >> 4][col l & 15] and D[row (l >> 4) + 4 reg][col l & 15].
+// In xxt the contraction index is 4 COLUMNS of X and an operand fragment 16 consecutive rows of them -- contiguous pieces of
+// the column-major source, where syrk_kernels.hpp has to turn its slabs round.  Every sum is taken in a fixed order: two
+// fits of the same data return the same bits.  fp32 storage becomes fp64 where a panel is staged; all arithmetic is fp64.
+#pragma once
+#include "common.hpp"
+#include "small_kernels.hpp"
+#include "syrk_kernels.hpp"
+
+namespace plsk {
+
+constexpr int DUAL_NMAX = 8192;  // rows of a DUAL fit: G = X X^T is N x N doubles (512 MB at the cap)
+constexpr int DUAL_MMAX = MMAX;  // responses: the direction solve of one workgroup (dominant_eigvec_lds)
+constexpr int DUAL_RPT = DUAL_NMAX / UPD_THREADS;  // rows per thread of dual_step_kernel
+
+constexpr int XXT_TB = 128;           // block of G per workgroup
+constexpr int XXT_KC = 16;            // columns of X per staged slab
+constexpr int XXT_LDR = XXT_TB + 16;  // rows of a staged column, padded: the operand reads of a half-wave (16 rows of 2 columns) hit 32 distinct bank pairs
+
+// blockIdx.x enumerates the nbn (nbn + 1) / 2 blocks (bi <= bj), blockIdx.y the split of the columns of X: slabs
+// [y per_split, (y + 1) per_split).  Every workgroup writes its whole 128 x 128 block of part[y] (zeros when it has no slab).
+template <typename T>
+__global__ __launch_bounds__(256, 2) void xxt_kernel(const T *__restrict__ X, i64 ldx, int N, i64 K, int nbn, i64 per_split,
+                                                     double *__restrict__ part) {
+    __shared__ double As[XXT_KC * XXT_LDR], Bsm[XXT_KC * XXT_LDR];
+    int bi = 0, rem = blockIdx.x;
+    while (rem >= nbn - bi) { rem -= nbn - bi; ++bi; }
+    const int bj = bi + rem;
+    const bool diag = (bi == bj);
+    const double *Bs = diag ? As : Bsm;
+
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int sr = tid & (XXT_TB - 1), sc = tid >> 7;  // staging: row of the panel, first of its 8 columns (sc, sc + 2, ...)
+    const int a0 = (wv >> 1) * 64, b0 = (wv & 1) * 64;
+    const int li = lane & 15, lq = lane >> 4;
+    const int ra = bi * XXT_TB + sr, rb = bj * XXT_TB + sr;
+
+    f64x4 acc[4][4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int n = 0; n < 4; ++n) acc[m][n] = f64x4{0.0, 0.0, 0.0, 0.0};
+
+    const i64 nslabs = (K + XXT_KC - 1) / XXT_KC;
+    const i64 s0 = min(nslabs, (i64)blockIdx.y * per_split), s1 = min(nslabs, s0 + per_split);
+    double ga[XXT_KC / 2], gb[XXT_KC / 2];
+    auto load_slab = [&](i64 s) {
+#pragma unroll
+        for (int j = 0; j < XXT_KC / 2; ++j) {
+            const i64 col = s * XXT_KC + sc + 2 * j;
+            ga[j] = (ra < N && col < K) ? (double)X[ra + col * ldx] : 0.0;
+            gb[j] = (!diag && rb < N && col < K) ? (double)X[rb + col * ldx] : 0.0;
+        }
+    };
+    if (s0 < s1) load_slab(s0);
+    for (i64 s = s0; s < s1; ++s) {
+        __syncthreads();  // everyone is done reading the previous slab
+#pragma unroll
+        for (int j = 0; j < XXT_KC / 2; ++j) {
+            As[(sc + 2 * j) * XXT_LDR + sr] = ga[j];
+            if (!diag) Bsm[(sc + 2 * j) * XXT_LDR + sr] = gb[j];
+        }
+        __syncthreads();
+        if (s + 1 < s1) load_slab(s + 1);  // in flight under the slab's MFMAs
+#pragma unroll
+        for (int kk = 0; kk < XXT_KC; kk += 4) {
+            double a[4], b[4];
+#pragma unroll
+            for (int m = 0; m < 4; ++m) a[m] = As[(kk + lq) * XXT_LDR + a0 + 16 * m + li];
+#pragma unroll
+            for (int n = 0; n < 4; ++n) b[n] = Bs[(kk + lq) * XXT_LDR + b0 + 16 * n + li];
+#pragma unroll
+            for (int m = 0; m < 4; ++m)
+#pragma unroll
+                for (int n = 0; n < 4; ++n) acc[m][n] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[m], b[n], acc[m][n], 0, 0, 0);
+        }
+    }
+    double *out = part + (i64)blockIdx.y * ((i64)N * N);
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int n = 0; n < 4; ++n)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int gi = bi * XXT_TB + a0 + 16 * m + lq + 4 * r;
+                const int gj = bj * XXT_TB + b0 + 16 * n + li;
+                if (gi < N && gj < N) out[gi + (i64)gj * N] = acc[m][n][r];
+            }
+}
+
+// G[i, j] = G[j, i] = sum over the splits, in split order, of the entry (i, j) on or above the diagonal.
+// grid (blocks, 64), 256 threads: one entry of a block per thread.
+__global__ __launch_bounds__(256) void xxt_reduce_kernel(const double *__restrict__ part, int nsplit, int N, int nbn,
+                                                         double *__restrict__ G) {
+    int bi = 0, rem = blockIdx.x;
+    while (rem >= nbn - bi) { rem -= nbn - bi; ++bi; }
+    const int bj = bi + rem;
+    const int e = blockIdx.y * 256 + threadIdx.x;
+    const int i = bi * XXT_TB + (e & (XXT_TB - 1)), j = bj * XXT_TB + e / XXT_TB;
+    if (i >= N || j >= N || i > j) return;
+    const i64 NN = (i64)N * N;
+    const double *p = part + i + (i64)j * N;
+    double s = 0.0;
+    for (int z = 0; z < nsplit; ++z) s += p[(i64)z * NN];
+    G[i + (i64)j * N] = s;
+    G[j + (i64)i * N] = s;
+}
+
+// Z[i, m] = sum_j G[j, i] Ya[j, m] (G is symmetric: column i is row i): one wave per i, lanes along j, the lane sums added by
+// wave_sum.  MT >= M accumulators per lane.
+template <int MT>
+__global__ __launch_bounds__(256) void dual_gy_kernel(const double *__restrict__ G, const double *__restrict__ Ya, int N, int M,
+                                                      double *__restrict__ Z) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= N) return;  // (wave-uniform)
+    const double *g = G + (i64)i * N;
+    double acc[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) acc[m] = 0.0;
+    for (int j = lane; j < N; j += 64) {
+        const double gv = g[j];
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+            if (m < M) acc[m] = fma(gv, Ya[j + (i64)m * N], acc[m]);
+    }
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        const double s = wave_sum(acc[m]);
+        if (m < M && lane == 0) Z[i + (i64)m * N] = s;
+    }
+}
+
+// One component on N-sized data, one workgroup of 1024 threads; thread t owns the rows t, t + 1024, ... (at most DUAL_RPT).
+//   direction   M = 1: u = Y_a, g = Z.  M > 1: S = Y_a^T Z (= XY_a^T XY_a, src/pls.cpp:406), q^ its dominant eigenvector,
+//               u = Y_a q^, g = Z q^
+//   nw = sqrt(u^T g) = |X^T u| (:411);  c_j = t_j^T g / tt_j, t = (g - sum_j c_j t_j) / nw (the t = X r of :419);
+//   C[j, a] = c_j / nw = p_j^T w_a;  tt = t^T t, q = Y_a^T t / tt (:428), Y_a -= t q^T
+// Stores T64[:, a] = t, V[:, a] = u / nw, V[:, A + a] = t / tt, Q[:, a], ttv[a].  scr: N + A doubles (g, then c).
+__global__ __launch_bounds__(UPD_THREADS) void dual_step_kernel(const double *__restrict__ Z, double *__restrict__ Ya,
+                                                                double *__restrict__ T64, double *__restrict__ V,
+                                                                double *__restrict__ Q, double *__restrict__ C,
+                                                                double *__restrict__ ttv, double *__restrict__ scr, int N, int M,
+                                                                int A, int a, int power_iters) {
+    __shared__ UpdShared sh;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    double *gbuf = scr, *cbuf = scr + N;
+    double u[DUAL_RPT], g[DUAL_RPT], t[DUAL_RPT];
+    if (M > 1) {
+        // the M (M + 1) / 2 entries of S on or above the diagonal: a wave per entry
+        for (int e = wv; e < M * (M + 1) / 2; e += UPD_WAVES) {
+            int i = 0, r = e;
+            while (r >= M - i) { r -= M - i; ++i; }
+            const int j = i + r;
+            double s = 0.0;
+            for (int n = lane; n < N; n += 64) s = fma(Ya[n + (i64)i * N], Z[n + (i64)j * N], s);
+            s = wave_sum(s);
+            if (lane == 0) sh.Gs[i + j * M] = sh.Gs[j + i * M] = s;
+        }
+        __syncthreads();
+        dominant_eigvec_lds(sh.Gs, sh.Bs, sh.Cs, sh.qs, M, power_iters);
+    }
+    double part = 0.0;
+#pragma unroll
+    for (int i = 0; i < DUAL_RPT; ++i) {
+        const int n = tid + i * UPD_THREADS;
+        u[i] = g[i] = 0.0;
+        if (n < N) {
+            if (M > 1) {
+                for (int m = 0; m < M; ++m) {
+                    u[i] = fma(Ya[n + (i64)m * N], sh.qs[m], u[i]);
+                    g[i] = fma(Z[n + (i64)m * N], sh.qs[m], g[i]);
+                }
+            } else {
+                u[i] = Ya[n];
+                g[i] = Z[n];
+            }
+            gbuf[n] = g[i];
+        }
+        part = fma(u[i], g[i], part);
+    }
+    const double nw = sqrt(block_sum<UPD_WAVES>(part, sh.sred));  // (its barriers publish gbuf)
+    for (int j = wv; j < a; j += UPD_WAVES) {  // a wave per earlier score
+        double s = 0.0;
+        for (int n = lane; n < N; n += 64) s = fma(T64[n + (i64)j * N], gbuf[n], s);
+        s = wave_sum(s) / ttv[j];
+        if (lane == 0) {
+            cbuf[j] = s;
+            C[j + (i64)a * A] = s / nw;
+        }
+    }
+    __syncthreads();
+    part = 0.0;
+#pragma unroll
+    for (int i = 0; i < DUAL_RPT; ++i) {
+        const int n = tid + i * UPD_THREADS;
+        t[i] = 0.0;
+        if (n < N) {
+            double s = g[i];
+            for (int j = 0; j < a; ++j) s = fma(-cbuf[j], T64[n + (i64)j * N], s);
+            t[i] = s / nw;
+            T64[n + (i64)a * N] = t[i];
+        }
+        part = fma(t[i], t[i], part);
+    }
+    const double tt = block_sum<UPD_WAVES>(part, sh.sred);  // (... and T64[:, a])
+    for (int m = wv; m < M; m += UPD_WAVES) {  // a wave per response
+        double s = 0.0;
+        for (int n = lane; n < N; n += 64) s = fma(Ya[n + (i64)m * N], T64[n + (i64)a * N], s);
+        s = wave_sum(s) / tt;
+        if (lane == 0) {
+            sh.qs[m] = s;
+            Q[m + (i64)a * M] = s;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) ttv[a] = tt;
+#pragma unroll
+    for (int i = 0; i < DUAL_RPT; ++i) {
+        const int n = tid + i * UPD_THREADS;
+        if (n < N) {
+            for (int m = 0; m < M; ++m) Ya[n + (i64)m * N] = fma(-t[i], sh.qs[m], Ya[n + (i64)m * N]);
+            V[n + (i64)a * N] = u[i] / nw;
+            V[n + (i64)(A + a) * N] = t[i] / tt;
+        }
+    }
+}
+
+constexpr int XTV_KB = 64;   // columns of X per workgroup
+constexpr int XTV_RC = 64;   // rows per staged chunk
+constexpr int XTV_NC = 64;   // columns of V per sweep
+constexpr int XTV_LD = XTV_RC + 2;  // operand reads (lane: column l & 15, row l >> 4) hit 32 distinct bank pairs per half-wave
+constexpr size_t XTV_LDS_BYTES = (size_t)(XTV_KB + XTV_NC) * XTV_LD * 8;
+
+// out[k, c] = sum_n X[n, k] V[n, c0 + c] for the 64 columns k of this workgroup and nc <= 64 columns c: wave w owns the 16
+// columns k0 + 16 w .. of X (the MFMA's rows), the tiles of 16 columns of V are its columns, 4 rows of X the contraction.
+// Column c0 + c of V goes to W[:, c0 + c] when c0 + c < A, to P[:, c0 + c - A] otherwise; the block leaves through LDS so
+// that every store is 64 consecutive rows of an output column.
+// NCT: tiles of 16 columns of V the instantiation carries, ceil(nc / 16).
+template <typename T, int NCT>
+__global__ __launch_bounds__(256, 2) void dual_xtv_kernel(const T *__restrict__ X, i64 ldx, int N, i64 K, const double *__restrict__ V,
+                                                          int c0, int nc, int A, double *__restrict__ W, double *__restrict__ P) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char xtv_raw[];
+    double *Xs = reinterpret_cast<double *>(xtv_raw), *Vs = Xs + XTV_KB * XTV_LD;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int li = lane & 15, lq = lane >> 4;
+    const i64 k0 = (i64)blockIdx.x * XTV_KB;
+    f64x4 acc[NCT];
+#pragma unroll
+    for (int ct = 0; ct < NCT; ++ct) acc[ct] = f64x4{0.0, 0.0, 0.0, 0.0};
+    double gx[16], gv[16];
+    auto load_chunk = [&](int n0) {  // thread: row n0 + lane of the columns wv, wv + 4, ...
+        const int n = n0 + lane;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int c = wv + 4 * j;
+            gx[j] = (n < N && k0 + c < K) ? (double)X[n + (k0 + c) * ldx] : 0.0;
+            gv[j] = (n < N && c < nc) ? V[n + (i64)(c0 + c) * N] : 0.0;
+        }
+    };
+    load_chunk(0);
+    for (int n0 = 0; n0 < N; n0 += XTV_RC) {
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            Xs[(wv + 4 * j) * XTV_LD + lane] = gx[j];
+            Vs[(wv + 4 * j) * XTV_LD + lane] = gv[j];
+        }
+        __syncthreads();
+        if (n0 + XTV_RC < N) load_chunk(n0 + XTV_RC);
+#pragma unroll 2  // (fully unrolled the 80 operand reads are hoisted and spill)
+        for (int kk = 0; kk < XTV_RC; kk += 4) {
+            const double xa = Xs[(16 * wv + li) * XTV_LD + kk + lq];
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct)
+                acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa, Vs[(16 * ct + li) * XTV_LD + kk + lq], acc[ct], 0, 0, 0);
+        }
+    }
+    __syncthreads();
+    double *Os = Xs;  // [column c][row k of the block]
+#pragma unroll
+    for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Os[(16 * ct + li) * XTV_LD + 16 * wv + lq + 4 * r] = acc[ct][r];
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const int c = wv + 4 * j, cg = c0 + c;
+        if (c < nc && k0 + lane < K) {
+            double *o = cg < A ? W + (i64)cg * K : P + (i64)(cg - A) * K;
+            o[k0 + lane] = Os[c * XTV_LD + lane];
+        }
+    }
+}
+
+// r_a = w_a - sum_{j<a} C[j, a] r_j (src/pls.cpp:412-416 with p_j^T w_a = C[j, a]): a thread per row, no reduction over K;
+// C[j, a] is the same address in every lane (the scalar cache).
+__global__ __launch_bounds__(256) void dual_r_kernel(const double *__restrict__ W, const double *__restrict__ C, i64 K, int A,
+                                                     double *__restrict__ R) {
+    const i64 k = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (k >= K) return;
+    for (int a = 0; a < A; ++a) {
+        double r = W[k + (i64)a * K];
+        for (int j = 0; j < a; ++j) r = fma(-C[j + (i64)a * A], R[k + (i64)j * K], r);
+        R[k + (i64)a * K] = r;
+    }
+}
+
+template <typename TI, typename TO>
+__global__ __launch_bounds__(256) void dual_convert_kernel(const TI *__restrict__ src, i64 lds, TO *__restrict__ dst, i64 ldd, int N,
+                                                           int cols) {
+    const i64 e = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (i64)N * cols) return;
+    const i64 n = e % N, c = e / N;
+    dst[n + c * ldd] = (TO)src[n + c * lds];
+}
+
+}  // namespace plsk

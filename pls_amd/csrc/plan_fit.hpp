@@ -43,6 +43,9 @@ inline void resident_done(pls_hip_context *c) {
 template <typename T>
 int fit_device(pls_hip_context *c, const T *X, i64 ldx, const T *Y, i64 ldy, i64 N, int K, int M,
                int A, int method, double *W, double *P, double *Q, double *R, T *Tm, i64 ldt, double *B) {
+    // The sample-space plan (opt-in, never AUTO's choice): everything from G = X X^T, two sweeps over X (plan_dual.hpp)
+    if (method == PLS_HIP_KERNEL_TYPE1 && c->opt_algo == PLS_HIP_ALGO_DUAL)
+        return fit_dual<T>(c, X, ldx, Y, ldy, N, K, M, A, W, P, Q, R, Tm, ldt, B);
     // GRAM plan for a KERNEL_TYPE1 request: the K-sized loop runs on XX = X^T X exactly as KERNEL_TYPE2
     // does (no pass over X per component), then the scores are formed in one pass, T = X R.
     // AUTO: pick between the read-only pass plan and the Gram plan from a bandwidth / matrix-core cost

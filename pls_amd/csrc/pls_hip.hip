@@ -34,6 +34,7 @@
 #include "validation_kernels.hpp"
 #include "xdiag_kernels.hpp"
 #include "batch_kernels.hpp"
+#include "dual_kernels.hpp"
 #include "synth_kernels.hpp"
 #include "host_pipeline.hpp"
 #include "exchange_kernels.hpp"
@@ -44,6 +45,7 @@ using plsk::i64;
 #include "launch_products.hpp"
 #include "launch_update.hpp"
 #include "plan_common.hpp"
+#include "plan_dual.hpp"
 #include "plan_fit.hpp"
 #include "host_entry.hpp"
 #include "plan_validation.hpp"
@@ -121,7 +123,8 @@ int pls_hip_destroy(pls_hip_handle h) {
                       &h->cvidx, &h->cvx, &h->cvy, &h->cvws, &h->cve, &h->cvtx, &h->cvty, &h->cvtt, &h->cvm, &h->cvkeep, &h->cvred, &h->work, &h->hX, &h->hY,
                       &h->hT, &h->hW, &h->hP, &h->hQ, &h->hR, &h->hB, &h->hIn, &h->hOut, &h->valout, &h->valpart, &h->vale, &h->valacc, &h->valkeys,
                       &h->valhist, &h->xdS, &h->xdQ, &h->xdPT, &h->xdred, &h->xdtv, &h->xdoQ, &h->xdoT, &h->xdoS, &h->xdsmall,
-                      &h->bws, &h->bv, &h->bred, &h->bmsg, &h->bssy, &h->bY, &h->boR, &h->boQ, &h->bott, &h->boB, &h->bossy};
+                      &h->bws, &h->bv, &h->bred, &h->bmsg, &h->bssy, &h->bY, &h->boR, &h->boQ, &h->bott, &h->boB, &h->bossy,
+                      &h->dG, &h->dpart, &h->dV, &h->dT, &h->dY, &h->dZ, &h->dC, &h->dscr};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (void *q : h->graveyard) (void)hipFree(q);
@@ -149,7 +152,7 @@ int pls_hip_set_option(pls_hip_handle h, int option, int64_t value) {
     switch (option) {
         case PLS_HIP_OPT_ALGO:
             if (value != PLS_HIP_ALGO_KERNEL && value != PLS_HIP_ALGO_NIPALS && value != PLS_HIP_ALGO_GRAM &&
-                value != PLS_HIP_ALGO_AUTO)
+                value != PLS_HIP_ALGO_AUTO && value != PLS_HIP_ALGO_DUAL)
                 return fail(h, PLS_HIP_ERR_INVALID, "unknown algo");
             h->opt_algo = value;
             return PLS_HIP_OK;
@@ -274,6 +277,10 @@ int pls_hip_fit(pls_hip_handle h, const void *X, int64_t ldx, const void *Y, int
     if (!W || !P || !Q || !R) return fail(h, PLS_HIP_ERR_INVALID, "null W/P/Q/R");
     if (ldx < std::max<i64>(N, 1) || ldy < std::max<i64>(N, 1) || (T && ldt < std::max<i64>(N, 1)))
         return fail(h, PLS_HIP_ERR_INVALID, "leading dimension smaller than N");
+    // the sample-space plan refuses what it cannot take before anything is written (plan_dual.hpp)
+    const bool dual = method == PLS_HIP_KERNEL_TYPE1 && h->opt_algo == PLS_HIP_ALGO_DUAL;
+    if (dual)
+        if (const char *why = dual_refusal(h, N, M)) return fail(h, PLS_HIP_ERR_UNSUPPORTED, why);
     CHK(set_device(h));
     const size_t es = esize(dtype);
     const int Ki = (int)K, Mi = (int)M, Ai = (int)A;
@@ -326,8 +333,9 @@ int pls_hip_fit(pls_hip_handle h, const void *X, int64_t ldx, const void *Y, int
     // also sizes every workspace); second: the same enqueue sequence under stream capture (nothing allocates any more),
     // instantiated and launched; from the third on: hipGraphLaunch.  The kernel arguments are baked into the graph, so the key
     // is everything they derive from.
+    // (a DUAL fit is never captured: it simply runs)
     const bool graphable = h->opt_graph && mem == PLS_HIP_MEM_DEVICE && !h->reducer && h->opt_profile == 0 && !h->user_red &&
-                           h->stream != nullptr;  // (the legacy default stream cannot be captured)
+                           h->stream != nullptr && !dual;  // (the legacy default stream cannot be captured)
     std::vector<uint64_t> key;
     if (graphable) {
         key = {(uint64_t)(uintptr_t)X, (uint64_t)ldx, (uint64_t)(uintptr_t)Y, (uint64_t)ldy, (uint64_t)N, (uint64_t)K, (uint64_t)M,

@@ -103,7 +103,7 @@ Ctx make_context() {
         throw std::runtime_error("PLS: no usable MI355X (gfx950) device (pls_hip_group_create status " +
                                  std::to_string(rc) + "); this library has no CPU path");
     c->plain_device = devs[0];
-    // PLS_HIP_ALGO = auto (default) | kernel | nipals | gram.  auto: the Gram plan whenever X^T X came with the
+    // PLS_HIP_ALGO = auto (default) | kernel | nipals | gram | dual (the sample-space plan for short, wide X: opt-in).  auto: the Gram plan whenever X^T X came with the
     // upload (it is accumulated on the matrix cores while the rows cross PCIe) or the cost model favours it, the
     // reference's own operation sequence (kernel) otherwise; same results to rounding either way.
     const char *e = std::getenv("PLS_HIP_ALGO");
@@ -111,6 +111,7 @@ Ctx make_context() {
     pls_hip_group_set_option(c->g, PLS_HIP_OPT_ALGO,
                              a == "nipals" ? PLS_HIP_ALGO_NIPALS
                              : a == "gram" ? PLS_HIP_ALGO_GRAM
+                             : a == "dual" ? PLS_HIP_ALGO_DUAL
                              : a == "kernel" ? PLS_HIP_ALGO_KERNEL
                                              : PLS_HIP_ALGO_AUTO);
     return c;
