@@ -92,7 +92,9 @@ typedef enum { PLS_HIP_MEM_HOST = 0, PLS_HIP_MEM_DEVICE = 1 } pls_hip_mem;
  *           eigenvector is normalised in the response space from a differently rounded matrix); B does not depend on
  *           it.  PLS_HIP_OPT_FUSE, _DEFER and _WORK_LAYOUT do not apply; a DUAL fit is never captured by
  *           PLS_HIP_OPT_GRAPH, it simply runs.  Like GRAM it squares the singular values of X; unlike GRAM it
- *           orthogonalises every score against the earlier ones explicitly. */
+ *           orthogonalises every score against the earlier ones explicitly.
+ *           pls_hip_cv_folds on a handle with this option runs every fold from the same G: one sweep over X for the whole
+ *           call (see there). */
 typedef enum {
     PLS_HIP_ALGO_KERNEL = 0,
     PLS_HIP_ALGO_NIPALS = 1,
@@ -280,6 +282,15 @@ PLS_HIP_API int pls_hip_model_sse(pls_hip_handle h, const void *X, int64_t ldx, 
  * fold on the masked X instead (no X^T X at all).  Shapes that launch declines (M > 32, A > 4096, K > 16384, workspaces that do not fit) run as one
  * device refit per fold instead -- same results, num_folds fits.  The call returns after the work
  * has completed.
+ * Under PLS_HIP_ALGO_DUAL (no reducer, N <= 8192, M <= 32, PLS_HIP_CV_REFIT unset) the call is taken before all of these by
+ * the sample-space route: G = X X^T once -- the only pass over X, whatever A and num_folds are -- then every fold runs the
+ * plan's recursion on vectors of length N with its held-out rows masked (Y_0 = diag(mask) Y; the score of every row comes
+ * from G, so a held-out row's score under the fold's model is free), in rounds of as many folds as 4 GB of workspace and
+ * half of the free device memory hold (PLS_HIP_DUALCV_ROUND=n caps a round): per component one product G [Y_a of every
+ * fold] and one workgroup per fold.  Same E, any K, either storage type (fp64 arithmetic), either memory kind; two calls
+ * with the same arguments return the same bits.  A fold with fewer training rows than A has inf/NaN in its surplus columns,
+ * the earlier ones intact.  A call outside those limits routes as under the other plans (per-fold refits that the
+ * sample-space plan would refuse -- M > 32, more than 8192 training rows -- run under the default plan); a workspace that does not fit falls back to the routes above.
  * Row-sharded handle (a reducer installed, pls_hip_set_reducer): the call is a COLLECTIVE.  Every rank calls it
  * with the same K, M, A, test_idx, test_size, num_folds and dtype; X, Y are the rank's own block of N rows
  * (N may be 0), blocks contiguous in rank order (rank r owns global rows [sum_{s<r} N_s, + N_r), as

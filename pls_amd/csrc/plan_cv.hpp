@@ -135,6 +135,10 @@ int cv_folds_refit(pls_hip_context *h, const T *dX, i64 dldx, const T *dY, i64 d
     LAUNCH_CHECK(h);
     const double *saved_xx = h->pre_xx, *saved_xy = h->pre_xy;  // products of ALL rows: not a fold's
     h->pre_xx = h->pre_xy = nullptr;
+    // folds whose fit (N - ts training rows) the sample-space plan would refuse (plan_dual.hpp: dual_refusal) are fitted under
+    // the default plan
+    const i64 saved_algo = h->opt_algo;
+    if (saved_algo == PLS_HIP_ALGO_DUAL && dual_refusal(h, N - ts, M)) h->opt_algo = PLS_HIP_ALGO_KERNEL;
     std::vector<char> held(N, 0);
     std::vector<int64_t> keep(N);
     int rc = PLS_HIP_OK;
@@ -166,6 +170,7 @@ int cv_folds_refit(pls_hip_context *h, const T *dX, i64 dldx, const T *dY, i64 d
     }
     h->pre_xx = saved_xx;
     h->pre_xy = saved_xy;
+    h->opt_algo = saved_algo;
     return rc;
 }
 

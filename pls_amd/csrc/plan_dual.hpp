@@ -19,11 +19,10 @@ inline const char *dual_refusal(const pls_hip_context *c, i64 N, i64 M) {
     return nullptr;
 }
 
+// The sweep over X that both users of the plan begin with (the fit, the cross-validation folds of plan_dual_cv.hpp):
+// c->dG = G = X X^T on the matrix cores, one bracket of PLS_HIP_FAM_XTY.
 template <typename T>
-int fit_dual(pls_hip_context *c, const T *X, i64 ldx, const T *Y, i64 ldy, i64 N64, int K, int M, int A, double *W, double *P,
-             double *Q, double *R, T *Tm, i64 ldt, double *B) {
-    if (const char *why = dual_refusal(c, N64, M)) return fail(c, PLS_HIP_ERR_UNSUPPORTED, why);
-    const int N = (int)N64;
+int dual_gram(pls_hip_context *c, const T *X, i64 ldx, int N, int K) {
     const i64 NN = (i64)N * N, es = (i64)sizeof(T);
     // split of the sum over the columns of X: N is small, the blocks alone cannot fill the chip.  All workgroups resident at
     // once (two per CU) when the blocks allow it; the partial blocks stay below 4 GB.
@@ -36,27 +35,37 @@ int fit_dual(pls_hip_context *c, const T *X, i64 ldx, const T *Y, i64 ldy, i64 N
     S = (nslabs + per_split - 1) / per_split;  // (no split without a slab)
     CHK(ensure(c, c->dG, (size_t)NN * 8));
     CHK(ensure(c, c->dpart, (size_t)S * NN * 8));
+    double *G = (double *)c->dG.p, *part = (double *)c->dpart.p;
+    Range r_g("X X^T");
+    Scope s(c, PLS_HIP_FAM_XTY, (i64)N * K * es + NN * 8);
+    hipLaunchKernelGGL((plsk::xxt_kernel<T>), dim3((unsigned)nblk, (unsigned)S), dim3(256), 0, c->stream, X, ldx, N, (i64)K, nbn,
+                       per_split, part);
+    LAUNCH_CHECK(c);
+    hipLaunchKernelGGL(plsk::xxt_reduce_kernel, dim3((unsigned)nblk, plsk::XXT_TB * plsk::XXT_TB / 256), dim3(256), 0, c->stream,
+                       (const double *)part, (int)S, N, nbn, G);
+    LAUNCH_CHECK(c);
+    return PLS_HIP_OK;
+}
+
+template <typename T>
+int fit_dual(pls_hip_context *c, const T *X, i64 ldx, const T *Y, i64 ldy, i64 N64, int K, int M, int A, double *W, double *P,
+             double *Q, double *R, T *Tm, i64 ldt, double *B) {
+    if (const char *why = dual_refusal(c, N64, M)) return fail(c, PLS_HIP_ERR_UNSUPPORTED, why);
+    const int N = (int)N64;
+    const i64 NN = (i64)N * N, es = (i64)sizeof(T);
+    CHK(ensure(c, c->dG, (size_t)NN * 8));  // (dual_gram sizes it again: the pointers are taken before the sweep)
     CHK(ensure(c, c->dV, (size_t)N * 2 * A * 8));
     CHK(ensure(c, c->dT, (size_t)N * A * 8));
     CHK(ensure(c, c->dY, (size_t)N * M * 8));
     CHK(ensure(c, c->dZ, (size_t)N * M * 8));
     CHK(ensure(c, c->dC, (size_t)A * A * 8));
     CHK(ensure(c, c->dscr, (size_t)(N + 2 * (i64)A) * 8));
-    double *G = (double *)c->dG.p, *part = (double *)c->dpart.p, *V = (double *)c->dV.p, *T64 = (double *)c->dT.p;
+    double *G = (double *)c->dG.p, *V = (double *)c->dV.p, *T64 = (double *)c->dT.p;
     double *Ya = (double *)c->dY.p, *Z = (double *)c->dZ.p, *C = (double *)c->dC.p;
     double *ttv = (double *)c->dscr.p, *scr = ttv + A;
 
     Range r_fit("pls_hip_fit (sample space)");
-    {  // first sweep over X: G = X X^T
-        Range r_g("X X^T");
-        Scope s(c, PLS_HIP_FAM_XTY, (i64)N * K * es + NN * 8);
-        hipLaunchKernelGGL((plsk::xxt_kernel<T>), dim3((unsigned)nblk, (unsigned)S), dim3(256), 0, c->stream, X, ldx, N, (i64)K, nbn,
-                           per_split, part);
-        LAUNCH_CHECK(c);
-        hipLaunchKernelGGL(plsk::xxt_reduce_kernel, dim3((unsigned)nblk, plsk::XXT_TB * plsk::XXT_TB / 256), dim3(256), 0, c->stream,
-                           (const double *)part, (int)S, N, nbn, G);
-        LAUNCH_CHECK(c);
-    }
+    CHK(dual_gram<T>(c, X, ldx, N, K));  // first sweep over X: G = X X^T
     {
         Scope s(c, PLS_HIP_FAM_SMALL, (i64)N * M * (es + 8));
         hipLaunchKernelGGL((plsk::dual_convert_kernel<T, double>), dim3((unsigned)(((i64)N * M + 255) / 256)), dim3(256), 0, c->stream, Y,

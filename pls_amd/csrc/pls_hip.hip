@@ -35,6 +35,7 @@
 #include "xdiag_kernels.hpp"
 #include "batch_kernels.hpp"
 #include "dual_kernels.hpp"
+#include "dual_cv_kernels.hpp"
 #include "synth_kernels.hpp"
 #include "host_pipeline.hpp"
 #include "exchange_kernels.hpp"
@@ -93,6 +94,7 @@ int pls_hip_create(pls_hip_handle *out, int device, void *stream) {
         c->env.cv_refit = on("PLS_HIP_CV_REFIT");
         c->env.batch_refit = on("PLS_HIP_BATCH_REFIT");
         if (const char *e = getenv("PLS_HIP_BATCH_ROUND")) c->env.batch_round = atoll(e);
+        if (const char *e = getenv("PLS_HIP_DUALCV_ROUND")) c->env.dualcv_round = atoll(e);
         c->env.tail = !off("PLS_HIP_TAIL");
         {
             const char *e = getenv("PLS_HIP_TAIL");
@@ -124,7 +126,7 @@ int pls_hip_destroy(pls_hip_handle h) {
                       &h->hT, &h->hW, &h->hP, &h->hQ, &h->hR, &h->hB, &h->hIn, &h->hOut, &h->valout, &h->valpart, &h->vale, &h->valacc, &h->valkeys,
                       &h->valhist, &h->xdS, &h->xdQ, &h->xdPT, &h->xdred, &h->xdtv, &h->xdoQ, &h->xdoT, &h->xdoS, &h->xdsmall,
                       &h->bws, &h->bv, &h->bred, &h->bmsg, &h->bssy, &h->bY, &h->boR, &h->boQ, &h->bott, &h->boB, &h->bossy,
-                      &h->dG, &h->dpart, &h->dV, &h->dT, &h->dY, &h->dZ, &h->dC, &h->dscr};
+                      &h->dG, &h->dpart, &h->dV, &h->dT, &h->dY, &h->dZ, &h->dC, &h->dscr, &h->dcv};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (void *q : h->graveyard) (void)hipFree(q);
@@ -531,6 +533,7 @@ int pls_hip_sse_by_components(pls_hip_handle h, const void *S, int64_t lds, cons
 }  // extern "C"
 
 #include "plan_cv.hpp"
+#include "plan_dual_cv.hpp"
 #include "plan_batch.hpp"
 
 
@@ -578,7 +581,18 @@ int pls_hip_cv_folds(pls_hip_handle h, const void *X, int64_t ldx, const void *Y
     const bool tiny = M == 1 && plsk::tiny_fit_covers(N, (int)K, 1, (int)A, dldx, es) && !h->env.cv_refit && h->env.tiny;
     const bool tiny_m = plsk::tiny_fit_m_covers(N, (int)K, (int)M, (int)A, dldx, es) && !h->env.cv_refit && h->env.tiny;
     const bool micro = plsk::micro_fit_covers(N, (int)K, (int)M, (int)A, dldx, es) && !h->env.cv_refit && h->env.tiny;
-    if (micro) {
+    if (cv_dual_covers(h, N, M)) {  // the sample-space plan, an explicit opt-in: every fold from one X X^T
+        if (dtype == PLS_HIP_F64)
+            rc = cv_folds_dual<double>(h, (const double *)dX, dldx, (const double *)dY, dldy, (int)N, (int)K, (int)M, (int)A, test_idx,
+                                       (int)test_size, num_folds, dE);
+        else
+            rc = cv_folds_dual<float>(h, (const float *)dX, dldx, (const float *)dY, dldy, (int)N, (int)K, (int)M, (int)A, test_idx,
+                                      (int)test_size, num_folds, dE);
+        if (rc == PLS_HIP_ERR_ALLOC) h->err.clear();  // its workspace does not fit: the routes below
+    }
+    if (rc != PLS_HIP_ERR_ALLOC) {
+        // (the sample-space route took the call)
+    } else if (micro) {
         if (dtype == PLS_HIP_F64)
             rc = cv_folds_micro<double>(h, (const double *)dX, dldx, (const double *)dY, dldy, N, (int)K, (int)M, (int)A, test_idx,
                                         (int)test_size, num_folds, dE);

@@ -342,6 +342,10 @@ class Handle:
         """Residuals of batched cross-validation folds (cv_LOO / cv_LSO of the reference in one launch).
         test_idx: (num_folds, test_size) integer array of held-out rows.  Returns E with shape (M, nobs, A),
         nobs = num_folds * test_size: E[m] is what Residual.errors()[m] holds.
+        The handle's plan decides the route: with OPT_ALGO = ALGO_DUAL (no reducer, N <= 8192, M <= 32) every fold runs from
+        one G = X X^T -- one sweep over X for the whole call, whatever A and the number of folds are; the route for short,
+        wide X.  Every other handle routes by shape: single-launch fits per fold for small data,
+        the shared X^T X for K <= 16384, one refit per fold beyond.
         On a row-sharded handle (attach_reducer / attach_ipc_exchange) the call is a collective: every rank calls it with
         its own block of rows (possibly none) and the same A and test_idx, whose entries are GLOBAL row indices (blocks
         contiguous in rank order, as pls_amd.distributed.row_partition makes them); every rank receives the full E."""
@@ -841,14 +845,16 @@ class Model:
     # ---- cross-validation (reference include/PLS/pls.h:235-241, src/pls.cpp:469-549) -------------------
     # Each returns the residual tensor E of shape (M, nobs, A): E[m] is Residual.errors()[m].
     def cv_LOO(self):
-        """leave-one-out: fold i refits on all rows but i (all folds in one batched device call)"""
+        """leave-one-out: fold i refits on all rows but i (all folds in one batched device call).  The handle's plan decides
+        the route (Handle.cv_folds): under ALGO_DUAL every fold runs from one X X^T."""
         n = self._X.shape[0]
         return self.handle.cv_folds(self._X, self._Y, self.A, np.arange(n)[:, None])
 
     def cv_LSO(self, test_fraction: float, num_trials: int, rng=None):
         """leave-some-out: num_trials random splits with round(test_fraction*N) held-out rows each.
         The reference draws its splits from std::shuffle on a std::mt19937 (src/pls.cpp:218-227);
-        here they come from a numpy Generator (pass one for reproducibility)."""
+        here they come from a numpy Generator (pass one for reproducibility).  The handle's plan decides the route
+        (Handle.cv_folds): under ALGO_DUAL every fold runs from one X X^T."""
         n = self._X.shape[0]
         ts = int(test_fraction * n + 0.5)
         if ts == 0 or ts == n:
