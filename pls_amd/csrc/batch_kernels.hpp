@@ -1,13 +1,11 @@
 // Many response sets against one X (pls_hip_fit_batch): every problem b is Model::plsr(X, Y_b, KERNEL_TYPE2)
 // (src/pls.cpp:390-437) on the shared XX = X^T X and its own XY_b = X^T Y_b.
 //
-//   xtg_kernel          the wide product X^T G (G = the columns of a round's problems, hundreds to thousands of them) on
-//                       v_mfma_f64_16x16x4_f64: the operand staging of an OFF-DIAGONAL block of the register-staged SYRK
-//                       (syrk_kernels.hpp, syrk_kernel) with the second panel taken from G.  A workgroup = 4 waves = a
-//                       128 x 128 block of the result, each wave a 64 x 64 quadrant of 4 x 4 MFMA tiles; the rows are
-//                       split over gridDim.y workgroups whose partial blocks reduce_partials_kernel adds in fixed order.
-//                       The same kernel with X := XX (symmetric: XX^T = XX), G := the current r of every problem and ONE
-//                       row split is the component step's GEMM V = XX [r_0 r_1 ...]: no split-K, no atomics.
+//   xtg_kernel<T, false>  (syrk_kernels.hpp) the wide product X^T G (G = the columns of a round's problems, hundreds to
+//                       thousands of them) on v_mfma_f64_16x16x4_f64; the rows are split over gridDim.y workgroups whose
+//                       partial blocks reduce_partials_kernel adds in fixed order.  The same kernel with X := XX (symmetric:
+//                       XX^T = XX), G := the current r of every problem and ONE row split is the component step's GEMM
+//                       V = XX [r_0 r_1 ...] (launch_sym_product): no split-K, no atomics.
 //   batch_step_kernel   one workgroup per problem: tt_b = r_b^T v_b, then component_update_call on [v_b, tt_b] -- p, q, the
 //                       deflation of XY_b and the next w and r, the sequence cv_folds_kernel runs per fold.
 //   batch_ssy / pack / finish / tt: the K- and M-sized bookkeeping around them.
@@ -17,101 +15,6 @@
 #include "syrk_kernels.hpp"
 
 namespace plsk {
-
-typedef double bk_f64x4 __attribute__((ext_vector_type(4)));
-
-// out[split][a + b * ldo] = sum over the split's rows i of X[i, a] * G[i, b]     (a < K, b < C)
-// grid = (ceil(K/128) * nbc, row splits), nbc = ceil(C/128); 256 threads; dynamic LDS = SyrkCfg<T>::LDS_BYTES.
-// vec != 0: X, G are 16-byte aligned with ld % V == 0 (whole V-row packs are loaded at once); 0: element by element.
-template <typename T>
-__global__ __launch_bounds__(256, 2) void xtg_kernel(const T *__restrict__ X, i64 ldx, const T *__restrict__ G, i64 ldg, i64 N,
-                                                     int K, int C, int nbc, int vec, double *__restrict__ out, i64 ldo,
-                                                     i64 pstride) {
-    constexpr int V = SyrkCfg<T>::V, RB = SyrkCfg<T>::RB, LDP = SyrkCfg<T>::LDP;
-    extern __shared__ __attribute__((aligned(16))) unsigned char xtg_raw[];  // As[TB][LDP], Bs[TB][LDP]
-    T *As = reinterpret_cast<T *>(xtg_raw), *Bs = As + SYRK_TB * LDP;
-
-    const int bi = blockIdx.x / nbc, bj = blockIdx.x % nbc;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int rp = tid & 15, cgi = tid >> 4;  // staging map: row group (V rows), column group; 8 columns per thread and panel
-    const int a0 = (wv >> 1) * 64, b0 = (wv & 1) * 64;
-    const int li = lane & 15, lq = lane >> 4;
-
-    bk_f64x4 acc[4][4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int n = 0; n < 4; ++n) acc[m][n] = bk_f64x4{0.0, 0.0, 0.0, 0.0};
-
-    const i64 nslabs = (N + RB - 1) / RB;
-    Pack<T, V> ga[8], gb[8];
-
-    auto load_slab = [&](i64 s) {
-        const i64 r0 = s * RB + V * rp;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int ca = bi * SYRK_TB + cgi + 16 * j, cb = bj * SYRK_TB + cgi + 16 * j;
-#pragma unroll
-            for (int e = 0; e < V; ++e) ga[j].v[e] = gb[j].v[e] = (T)0;
-            if (vec && r0 + V <= N) {
-                if (ca < K) ga[j] = ld_pack<T, V>(X + r0 + (i64)ca * ldx);
-                if (cb < C) gb[j] = ld_pack<T, V>(G + r0 + (i64)cb * ldg);
-            } else if (r0 < N) {  // ragged last rows, unaligned layouts: the missing slots stay zero
-                for (int e = 0; e < V; ++e)
-                    if (r0 + e < N) {
-                        if (ca < K) ga[j].v[e] = X[r0 + e + (i64)ca * ldx];
-                        if (cb < C) gb[j].v[e] = G[r0 + e + (i64)cb * ldg];
-                    }
-            }
-        }
-    };
-    auto store_slab = [&]() {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int c = cgi + 16 * j;
-            constexpr int H = 8 / sizeof(T);
-#pragma unroll
-            for (int e = 0; e < V; e += H) {
-                *reinterpret_cast<Pack<T, H> *>(As + c * LDP + V * rp + e) = *reinterpret_cast<const Pack<T, H> *>(&ga[j].v[e]);
-                *reinterpret_cast<Pack<T, H> *>(Bs + c * LDP + V * rp + e) = *reinterpret_cast<const Pack<T, H> *>(&gb[j].v[e]);
-            }
-        }
-    };
-
-    const i64 per_split = (nslabs + gridDim.y - 1) / gridDim.y;  // a contiguous range of slabs per row split
-    const i64 s_end = min(nslabs, (i64)(blockIdx.y + 1) * per_split);
-    for (i64 s = (i64)blockIdx.y * per_split; s < s_end; ++s) {
-        load_slab(s);
-        __syncthreads();  // everyone is done reading the previous slab
-        store_slab();
-        __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < RB; kk += 4) {
-            double a[4], b[4];
-#pragma unroll
-            for (int m = 0; m < 4; ++m) a[m] = (double)As[(a0 + 16 * m + li) * LDP + kk + lq];
-#pragma unroll
-            for (int n = 0; n < 4; ++n) b[n] = (double)Bs[(b0 + 16 * n + li) * LDP + kk + lq];
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-#pragma unroll
-                for (int n = 0; n < 4; ++n) acc[m][n] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[m], b[n], acc[m][n], 0, 0, 0);
-        }
-    }
-
-    // f64 C/D layout: lane holds D[row = (lane >> 4) + 4 * reg][col = lane & 15]; row <-> column of X, col <-> column of G
-    double *o = out + (i64)blockIdx.y * pstride;
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int n = 0; n < 4; ++n)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int ga_ = bi * SYRK_TB + a0 + 16 * m + lq + 4 * r;
-                const int gb_ = bj * SYRK_TB + b0 + 16 * n + li;
-                if (ga_ < K && gb_ < C) o[ga_ + (i64)gb_ * ldo] = acc[m][n][r];
-            }
-}
 
 // ssy[c] = sum_i G[i, c]^2: thread-strided sums, waves in order.   grid = C workgroups of WG threads
 template <typename T>

@@ -9,10 +9,11 @@
 //
 //   dual_cv_init_kernel   per fold of a round: the position of every row in the fold's test set (-1: a training row),
 //                         Y_0 = diag(m) Y, the running predictions of the held-out rows = 0
-//   dual_cv_step_kernel   one component of every fold of the round, one workgroup per fold: dual_step_kernel with the mask,
-//                         plus the predictions of the held-out rows and column a of E
-// The round's product Z = G [Y_a(0) | Y_a(1) | ...] between them is xtg_kernel<double> with X := G (batch_kernels.hpp) or,
-// for at most 32 columns, dual_gy_kernel.  Every sum is taken in a fixed order; nothing waits on another workgroup.
+//   dual_cv_step_kernel   one component of every fold of the round, one workgroup per fold: the body of dual_step_kernel
+//                         with the mask (dual_step_body<true>, dual_kernels.hpp), plus the predictions of the held-out rows
+//                         and column a of E
+// The round's product Z = G [Y_a(0) | Y_a(1) | ...] between them is xtg_kernel<double, false> with X := G (launch_sym_product)
+// or, for at most 32 columns, dual_gy_kernel.  Every sum is taken in a fixed order; nothing waits on another workgroup.
 #pragma once
 #include "dual_kernels.hpp"
 
@@ -37,109 +38,15 @@ __global__ __launch_bounds__(256) void dual_cv_init_kernel(const double *__restr
     for (int e = tid; e < ts * M; e += 256) pred[(i64)f * ts * M + e] = 0.0;
 }
 
-// Component a of fold blockIdx.x of the round (fold0 + blockIdx.x of the call); thread t owns the rows t, t + 1024, ...
-// (at most DUAL_RPT).  The sequence of dual_step_kernel; what differs:
-//   c_j and tt sum over the training rows only (pos < 0); t is formed and stored for every row;
-//   Y_a is deflated on the training rows; on a held-out row i of the fold pred[i, m] += t q_m and
-//   E[m][fold * ts + i, a] = Y[row, m] - pred[i, m] (E: M matrices of nobs x A, column-major).
-// Per fold: Ya, Z (N x M), T64 (N x A), ttv (A), scr (N + A: g, then c), pos (N), pred (ts x M).
+// Component a of every fold of the round, one workgroup per fold (fold0 + blockIdx.x of the call): dual_step_body<true>.
 __global__ __launch_bounds__(UPD_THREADS) void dual_cv_step_kernel(const double *__restrict__ Zall, double *__restrict__ Yall,
                                                                    double *__restrict__ Tall, double *__restrict__ ttall,
                                                                    double *__restrict__ scrall, const int *__restrict__ posall,
                                                                    double *__restrict__ predall, const double *__restrict__ Y64,
                                                                    double *__restrict__ E, int N, int M, int A, int a, int ts,
                                                                    i64 fold0, i64 nobs, int power_iters) {
-    __shared__ UpdShared sh;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const i64 f = blockIdx.x;
-    const double *Z = Zall + f * M * N;
-    double *Ya = Yall + f * M * N, *T64 = Tall + f * (i64)N * A, *ttv = ttall + f * A;
-    double *gbuf = scrall + f * (N + A), *cbuf = gbuf + N;
-    const int *pos = posall + f * N;
-    double *pred = predall + f * ts * M;
-    double g[DUAL_RPT], t[DUAL_RPT];
-    int ps[DUAL_RPT];
-    if (M > 1) {
-        // the M (M + 1) / 2 entries of S = Y_a^T Z on or above the diagonal: a wave per entry
-        for (int e = wv; e < M * (M + 1) / 2; e += UPD_WAVES) {
-            int i = 0, r = e;
-            while (r >= M - i) { r -= M - i; ++i; }
-            const int j = i + r;
-            double s = 0.0;
-            for (int n = lane; n < N; n += 64) s = fma(Ya[n + (i64)i * N], Z[n + (i64)j * N], s);
-            s = wave_sum(s);
-            if (lane == 0) sh.Gs[i + j * M] = sh.Gs[j + i * M] = s;
-        }
-        __syncthreads();
-        dominant_eigvec_lds(sh.Gs, sh.Bs, sh.Cs, sh.qs, M, power_iters);
-    }
-    double part = 0.0;
-#pragma unroll
-    for (int i = 0; i < DUAL_RPT; ++i) {
-        const int n = tid + i * UPD_THREADS;
-        double u = 0.0;
-        g[i] = 0.0;
-        ps[i] = -1;
-        if (n < N) {
-            ps[i] = pos[n];
-            if (M > 1) {
-                for (int m = 0; m < M; ++m) {
-                    u = fma(Ya[n + (i64)m * N], sh.qs[m], u);
-                    g[i] = fma(Z[n + (i64)m * N], sh.qs[m], g[i]);
-                }
-            } else {
-                u = Ya[n];
-                g[i] = Z[n];
-            }
-            gbuf[n] = g[i];
-        }
-        part = fma(u, g[i], part);  // (u is zero on the held-out rows)
-    }
-    const double nw = sqrt(block_sum<UPD_WAVES>(part, sh.sred));  // (its barriers publish gbuf)
-    for (int j = wv; j < a; j += UPD_WAVES) {  // a wave per earlier score, the training rows
-        double s = 0.0;
-        for (int n = lane; n < N; n += 64) s = fma(pos[n] < 0 ? T64[n + (i64)j * N] : 0.0, gbuf[n], s);
-        s = wave_sum(s) / ttv[j];
-        if (lane == 0) cbuf[j] = s;
-    }
-    __syncthreads();
-    part = 0.0;
-#pragma unroll
-    for (int i = 0; i < DUAL_RPT; ++i) {
-        const int n = tid + i * UPD_THREADS;
-        t[i] = 0.0;
-        if (n < N) {
-            double s = g[i];
-            for (int j = 0; j < a; ++j) s = fma(-cbuf[j], T64[n + (i64)j * N], s);
-            t[i] = s / nw;
-            T64[n + (i64)a * N] = t[i];
-        }
-        if (ps[i] < 0) part = fma(t[i], t[i], part);
-    }
-    const double tt = block_sum<UPD_WAVES>(part, sh.sred);  // (... and T64[:, a])
-    for (int m = wv; m < M; m += UPD_WAVES) {  // a wave per response (Y_a is zero on the held-out rows)
-        double s = 0.0;
-        for (int n = lane; n < N; n += 64) s = fma(Ya[n + (i64)m * N], T64[n + (i64)a * N], s);
-        s = wave_sum(s) / tt;
-        if (lane == 0) sh.qs[m] = s;
-    }
-    __syncthreads();
-    if (tid == 0) ttv[a] = tt;
-#pragma unroll
-    for (int i = 0; i < DUAL_RPT; ++i) {
-        const int n = tid + i * UPD_THREADS;
-        if (n >= N) continue;
-        if (ps[i] < 0) {
-            for (int m = 0; m < M; ++m) Ya[n + (i64)m * N] = fma(-t[i], sh.qs[m], Ya[n + (i64)m * N]);
-        } else {
-            double *e = E + (i64)a * nobs + (fold0 + f) * ts + ps[i];
-            for (int m = 0; m < M; ++m) {
-                const double p = fma(t[i], sh.qs[m], pred[ps[i] + (i64)m * ts]);
-                pred[ps[i] + (i64)m * ts] = p;
-                e[(i64)m * nobs * A] = Y64[n + (i64)m * N] - p;
-            }
-        }
-    }
+    dual_step_body<true>(Zall, Yall, Tall, ttall, scrall, N, M, A, a, power_iters, nullptr, nullptr, nullptr, posall, predall, Y64, E,
+                         ts, fold0, nobs);
 }
 
 }  // namespace plsk

@@ -1,11 +1,13 @@
 // dual_kernels.hpp -- the kernels of the sample-space plan (PLS_HIP_ALGO_DUAL, plan_dual.hpp): a fit of a short, wide X from
 // G = X X^T (N x N) instead of from X^T X (K x K).
 //
-//   xxt_kernel            G = X X^T on v_mfma_f64_16x16x4_f64, the blocks on or above the diagonal, the sum over the columns of
-//                         X split over workgroups; xxt_reduce_kernel adds the partial blocks in split order and mirrors them
+//   xxt_kernel            G = X X^T on v_mfma_f64_16x16x4_f64 (its own staging around the block core of mfma_block.hpp), the
+//                         blocks on or above the diagonal, the sum over the columns of X split over workgroups;
+//                         xxt_reduce_kernel adds the partial blocks in split order and mirrors them
 //   dual_gy_kernel        Z = G Y_a (N x M): one wave per column of the symmetric G, the whole chip
 //   dual_step_kernel      everything else of a component, N (M + a) work, ONE workgroup: direction, norm, orthogonalisation
-//                         of the score against the earlier ones, loading of Y, deflation of Y_a
+//                         of the score against the earlier ones, loading of Y, deflation of Y_a (dual_step_body, which the
+//                         cross-validation folds of dual_cv_kernels.hpp run with their training-row masks)
 //   dual_xtv_kernel       [W | P] = X^T [U | T diag(1/tt)], up to 64 columns per sweep over X, on the matrix cores
 //   dual_r_kernel         r_a = w_a - sum_{j<a} C[j, a] r_j, a thread per row of R
 //   dual_convert_kernel   Y -> fp64 working copy, fp64 scores -> T in the storage type
@@ -35,23 +37,17 @@ template <typename T>
 __global__ __launch_bounds__(256, 2) void xxt_kernel(const T *__restrict__ X, i64 ldx, int N, i64 K, int nbn, i64 per_split,
                                                      double *__restrict__ part) {
     __shared__ double As[XXT_KC * XXT_LDR], Bsm[XXT_KC * XXT_LDR];
-    int bi = 0, rem = blockIdx.x;
-    while (rem >= nbn - bi) { rem -= nbn - bi; ++bi; }
-    const int bj = bi + rem;
+    int bi, bj;
+    tri_block(blockIdx.x, nbn, bi, bj);
     const bool diag = (bi == bj);
     const double *Bs = diag ? As : Bsm;
 
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     const int sr = tid & (XXT_TB - 1), sc = tid >> 7;  // staging: row of the panel, first of its 8 columns (sc, sc + 2, ...)
-    const int a0 = (wv >> 1) * 64, b0 = (wv & 1) * 64;
-    const int li = lane & 15, lq = lane >> 4;
     const int ra = bi * XXT_TB + sr, rb = bj * XXT_TB + sr;
-
+    const QuadMap q;
     f64x4 acc[4][4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int n = 0; n < 4; ++n) acc[m][n] = f64x4{0.0, 0.0, 0.0, 0.0};
+    quad_zero(acc);
 
     const i64 nslabs = (K + XXT_KC - 1) / XXT_KC;
     const i64 s0 = min(nslabs, (i64)blockIdx.y * per_split), s1 = min(nslabs, s0 + per_split);
@@ -75,38 +71,17 @@ __global__ __launch_bounds__(256, 2) void xxt_kernel(const T *__restrict__ X, i6
         __syncthreads();
         if (s + 1 < s1) load_slab(s + 1);  // in flight under the slab's MFMAs
 #pragma unroll
-        for (int kk = 0; kk < XXT_KC; kk += 4) {
-            double a[4], b[4];
-#pragma unroll
-            for (int m = 0; m < 4; ++m) a[m] = As[(kk + lq) * XXT_LDR + a0 + 16 * m + li];
-#pragma unroll
-            for (int n = 0; n < 4; ++n) b[n] = Bs[(kk + lq) * XXT_LDR + b0 + 16 * n + li];
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-#pragma unroll
-                for (int n = 0; n < 4; ++n) acc[m][n] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[m], b[n], acc[m][n], 0, 0, 0);
-        }
+        for (int kk = 0; kk < XXT_KC; kk += 4) quad_step<1, XXT_LDR>(As, Bs, q, kk, acc);
     }
-    double *out = part + (i64)blockIdx.y * ((i64)N * N);
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int n = 0; n < 4; ++n)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int gi = bi * XXT_TB + a0 + 16 * m + lq + 4 * r;
-                const int gj = bj * XXT_TB + b0 + 16 * n + li;
-                if (gi < N && gj < N) out[gi + (i64)gj * N] = acc[m][n][r];
-            }
+    quad_store(acc, q, part + (i64)blockIdx.y * ((i64)N * N), (i64)N, bi * XXT_TB, bj * XXT_TB, N, N, false);
 }
 
 // G[i, j] = G[j, i] = sum over the splits, in split order, of the entry (i, j) on or above the diagonal.
 // grid (blocks, 64), 256 threads: one entry of a block per thread.
 __global__ __launch_bounds__(256) void xxt_reduce_kernel(const double *__restrict__ part, int nsplit, int N, int nbn,
                                                          double *__restrict__ G) {
-    int bi = 0, rem = blockIdx.x;
-    while (rem >= nbn - bi) { rem -= nbn - bi; ++bi; }
-    const int bj = bi + rem;
+    int bi, bj;
+    tri_block(blockIdx.x, nbn, bi, bj);
     const int e = blockIdx.y * 256 + threadIdx.x;
     const int i = bi * XXT_TB + (e & (XXT_TB - 1)), j = bj * XXT_TB + e / XXT_TB;
     if (i >= N || j >= N || i > j) return;
@@ -147,23 +122,37 @@ __global__ __launch_bounds__(256) void dual_gy_kernel(const double *__restrict__
 //   direction   M = 1: u = Y_a, g = Z.  M > 1: S = Y_a^T Z (= XY_a^T XY_a, src/pls.cpp:406), q^ its dominant eigenvector,
 //               u = Y_a q^, g = Z q^
 //   nw = sqrt(u^T g) = |X^T u| (:411);  c_j = t_j^T g / tt_j, t = (g - sum_j c_j t_j) / nw (the t = X r of :419);
-//   C[j, a] = c_j / nw = p_j^T w_a;  tt = t^T t, q = Y_a^T t / tt (:428), Y_a -= t q^T
-// Stores T64[:, a] = t, V[:, a] = u / nw, V[:, A + a] = t / tt, Q[:, a], ttv[a].  scr: N + A doubles (g, then c).
-__global__ __launch_bounds__(UPD_THREADS) void dual_step_kernel(const double *__restrict__ Z, double *__restrict__ Ya,
-                                                                double *__restrict__ T64, double *__restrict__ V,
-                                                                double *__restrict__ Q, double *__restrict__ C,
-                                                                double *__restrict__ ttv, double *__restrict__ scr, int N, int M,
-                                                                int A, int a, int power_iters) {
+//   tt = t^T t, q = Y_a^T t / tt (:428), Y_a -= t q^T
+// CV = false, the fit (dual_step_kernel): also stores C[j, a] = c_j / nw = p_j^T w_a, V[:, a] = u / nw, V[:, A + a] = t / tt
+// and Q[:, a].
+// CV = true, fold blockIdx.x of a round of cross-validation folds (dual_cv_step_kernel, fold fold0 + blockIdx.x of the
+// call): the fold's slice of every array -- Ya, Z (N x M), T64 (N x A), ttv (A), scr (N + A), pos (N), pred (ts x M) -- and
+// the 0/1 mask of its training rows (pos < 0; dual_cv_kernels.hpp has the algebra):
+//   c_j and tt sum over the training rows only; t is formed and stored for every row;
+//   Y_a is deflated on the training rows; on a held-out row i of the fold pred[i, m] += t q_m and
+//   E[m][fold * ts + i, a] = Y[row, m] - pred[i, m] (E: M matrices of nobs x A, column-major).
+// Stores T64[:, a] = t and ttv[a].  scr: N + A doubles (g, then c).
+template <bool CV>
+__device__ __forceinline__ void dual_step_body(const double *__restrict__ Zall, double *__restrict__ Yall, double *__restrict__ Tall,
+                                               double *__restrict__ ttall, double *__restrict__ scrall, int N, int M, int A, int a,
+                                               int power_iters, double *__restrict__ V, double *__restrict__ Q,
+                                               double *__restrict__ C, const int *__restrict__ posall, double *__restrict__ predall,
+                                               const double *__restrict__ Y64, double *__restrict__ E, int ts, i64 fold0, i64 nobs) {
     __shared__ UpdShared sh;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    double *gbuf = scr, *cbuf = scr + N;
+    const i64 f = CV ? blockIdx.x : 0;
+    const double *Z = Zall + f * M * N;
+    double *Ya = Yall + f * M * N, *T64 = Tall + f * (i64)N * A, *ttv = ttall + f * A;
+    double *gbuf = scrall + f * (N + A), *cbuf = gbuf + N;
+    const int *pos = posall + f * N;
+    double *pred = predall + f * ts * M;
     double u[DUAL_RPT], g[DUAL_RPT], t[DUAL_RPT];
+    int ps[DUAL_RPT];  // (CV) the row's position in the fold's test set, -1: a training row
     if (M > 1) {
-        // the M (M + 1) / 2 entries of S on or above the diagonal: a wave per entry
+        // the M (M + 1) / 2 entries of S = Y_a^T Z on or above the diagonal: a wave per entry
         for (int e = wv; e < M * (M + 1) / 2; e += UPD_WAVES) {
-            int i = 0, r = e;
-            while (r >= M - i) { r -= M - i; ++i; }
-            const int j = i + r;
+            int i, j;
+            tri_block(e, M, i, j);
             double s = 0.0;
             for (int n = lane; n < N; n += 64) s = fma(Ya[n + (i64)i * N], Z[n + (i64)j * N], s);
             s = wave_sum(s);
@@ -177,7 +166,9 @@ __global__ __launch_bounds__(UPD_THREADS) void dual_step_kernel(const double *__
     for (int i = 0; i < DUAL_RPT; ++i) {
         const int n = tid + i * UPD_THREADS;
         u[i] = g[i] = 0.0;
+        ps[i] = -1;
         if (n < N) {
+            if constexpr (CV) ps[i] = pos[n];
             if (M > 1) {
                 for (int m = 0; m < M; ++m) {
                     u[i] = fma(Ya[n + (i64)m * N], sh.qs[m], u[i]);
@@ -189,16 +180,16 @@ __global__ __launch_bounds__(UPD_THREADS) void dual_step_kernel(const double *__
             }
             gbuf[n] = g[i];
         }
-        part = fma(u[i], g[i], part);
+        part = fma(u[i], g[i], part);  // (CV: u is zero on the held-out rows)
     }
     const double nw = sqrt(block_sum<UPD_WAVES>(part, sh.sred));  // (its barriers publish gbuf)
-    for (int j = wv; j < a; j += UPD_WAVES) {  // a wave per earlier score
+    for (int j = wv; j < a; j += UPD_WAVES) {  // a wave per earlier score (CV: the training rows)
         double s = 0.0;
-        for (int n = lane; n < N; n += 64) s = fma(T64[n + (i64)j * N], gbuf[n], s);
+        for (int n = lane; n < N; n += 64) s = fma((!CV || pos[n] < 0) ? T64[n + (i64)j * N] : 0.0, gbuf[n], s);
         s = wave_sum(s) / ttv[j];
         if (lane == 0) {
             cbuf[j] = s;
-            C[j + (i64)a * A] = s / nw;
+            if constexpr (!CV) C[j + (i64)a * A] = s / nw;
         }
     }
     __syncthreads();
@@ -213,16 +204,16 @@ __global__ __launch_bounds__(UPD_THREADS) void dual_step_kernel(const double *__
             t[i] = s / nw;
             T64[n + (i64)a * N] = t[i];
         }
-        part = fma(t[i], t[i], part);
+        if (ps[i] < 0) part = fma(t[i], t[i], part);
     }
     const double tt = block_sum<UPD_WAVES>(part, sh.sred);  // (... and T64[:, a])
-    for (int m = wv; m < M; m += UPD_WAVES) {  // a wave per response
+    for (int m = wv; m < M; m += UPD_WAVES) {  // a wave per response (CV: Y_a is zero on the held-out rows)
         double s = 0.0;
         for (int n = lane; n < N; n += 64) s = fma(Ya[n + (i64)m * N], T64[n + (i64)a * N], s);
         s = wave_sum(s) / tt;
         if (lane == 0) {
             sh.qs[m] = s;
-            Q[m + (i64)a * M] = s;
+            if constexpr (!CV) Q[m + (i64)a * M] = s;
         }
     }
     __syncthreads();
@@ -230,12 +221,30 @@ __global__ __launch_bounds__(UPD_THREADS) void dual_step_kernel(const double *__
 #pragma unroll
     for (int i = 0; i < DUAL_RPT; ++i) {
         const int n = tid + i * UPD_THREADS;
-        if (n < N) {
+        if (n >= N) continue;
+        if (ps[i] < 0) {
             for (int m = 0; m < M; ++m) Ya[n + (i64)m * N] = fma(-t[i], sh.qs[m], Ya[n + (i64)m * N]);
-            V[n + (i64)a * N] = u[i] / nw;
-            V[n + (i64)(A + a) * N] = t[i] / tt;
+            if constexpr (!CV) {
+                V[n + (i64)a * N] = u[i] / nw;
+                V[n + (i64)(A + a) * N] = t[i] / tt;
+            }
+        } else {
+            double *e = E + (i64)a * nobs + (fold0 + f) * ts + ps[i];
+            for (int m = 0; m < M; ++m) {
+                const double p = fma(t[i], sh.qs[m], pred[ps[i] + (i64)m * ts]);
+                pred[ps[i] + (i64)m * ts] = p;
+                e[(i64)m * nobs * A] = Y64[n + (i64)m * N] - p;
+            }
         }
     }
+}
+
+__global__ __launch_bounds__(UPD_THREADS) void dual_step_kernel(const double *__restrict__ Z, double *__restrict__ Ya,
+                                                                double *__restrict__ T64, double *__restrict__ V,
+                                                                double *__restrict__ Q, double *__restrict__ C,
+                                                                double *__restrict__ ttv, double *__restrict__ scr, int N, int M,
+                                                                int A, int a, int power_iters) {
+    dual_step_body<false>(Z, Ya, T64, ttv, scr, N, M, A, a, power_iters, V, Q, C, nullptr, nullptr, nullptr, nullptr, 0, 0, 0);
 }
 
 constexpr int XTV_KB = 64;   // columns of X per workgroup

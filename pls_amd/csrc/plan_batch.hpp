@@ -6,7 +6,6 @@
 namespace {
 
 constexpr i64 BATCH_MSG_CAP = (i64)1 << 20;    // values per slice of a message of whole problems on a sharded handle
-constexpr i64 BATCH_ROUND_BYTES = (i64)4 << 30;  // workspace of one round
 constexpr int BATCH_CB = 32;                   // column block of the fallback product (launch_xty)
 
 // the batched route's shapes: the bounds of cv_folds_kernel (everything M-sized in one workgroup's LDS, X^T X resident)
@@ -38,15 +37,14 @@ int batch_xtg(pls_hip_context *c, const T *X, i64 ldx, const T *G, i64 ldg, i64 
     if (mfma) {
         const int nbk = (K + plsk::SYRK_TB - 1) / plsk::SYRK_TB, nbc = (int)((C + plsk::SYRK_TB - 1) / plsk::SYRK_TB);
         const i64 nblocks = (i64)nbk * nbc, slots = 2 * (i64)c->num_cu, nslabs = (N + RB - 1) / RB;
-        // all workgroups resident at once when the blocks allow it, about eight residency waves otherwise (launch_syrk)
-        i64 S = nblocks <= slots ? slots / nblocks : (8 * slots + nblocks - 1) / nblocks;
+        i64 S = plsk::row_splits(nblocks, slots, 8);
         S = std::max<i64>(1, std::min<i64>(std::min<i64>(S, nslabs), 64));
         while (S > 1 && S * KC * 8 > ((i64)1 << 30)) --S;
         if (ensure(c, c->part, (size_t)S * KC * 8) == PLS_HIP_OK &&
-            plsk::raise_dynamic_lds((const void *)plsk::xtg_kernel<T>, (int)plsk::SyrkCfg<T>::LDS_BYTES)) {
+            plsk::raise_dynamic_lds((const void *)plsk::xtg_kernel<T, false>, (int)plsk::SyrkCfg<T>::LDS_BYTES)) {
             {
                 Scope s(c, PLS_HIP_FAM_XTY, (i64)N * K * sizeof(T) * nbc + (i64)N * C * sizeof(T) * nbk + S * KC * 8);
-                hipLaunchKernelGGL((plsk::xtg_kernel<T>), dim3((unsigned)nblocks, (unsigned)S), dim3(256), plsk::SyrkCfg<T>::LDS_BYTES,
+                hipLaunchKernelGGL((plsk::xtg_kernel<T, false>), dim3((unsigned)nblocks, (unsigned)S), dim3(256), plsk::SyrkCfg<T>::LDS_BYTES,
                                    c->stream, X, ldx, G, ldg, N, K, (int)C, nbc, 1, (double *)c->part.p, (i64)K, KC);
                 LAUNCH_CHECK(c);
             }
@@ -72,15 +70,8 @@ i64 batch_round_size(pls_hip_context *c, i64 K, i64 M, i64 A, i64 nprob) {
     const i64 KP = K + (K & 1);
     // workspace, V and r columns, the sliced product and the message, and the row-split partial blocks of the product
     const i64 per = (L.total + 2 * KP + plsk::RED_SLICES * (2 * K + 1) * M + M) * 8 + 16 * K * M * 8;
-    size_t fr = 0, tot = 0;
-    if (hipMemGetInfo(&fr, &tot) != hipSuccess) {
-        (void)hipGetLastError();
-        fr = (size_t)BATCH_ROUND_BYTES;
-    }
-    i64 nb = std::min<i64>(BATCH_ROUND_BYTES, (i64)(fr / 2)) / per;
-    nb = std::min<i64>(nb, ((i64)1 << 30) / std::max<i64>(1, (K + 1) * M));  // K * C and a message slice stay below 2^31 values
-    if (c->env.batch_round > 0) nb = std::min<i64>(nb, c->env.batch_round);
-    return std::max<i64>(0, std::min<i64>(nb, nprob));
+    // K * C and a message slice stay below 2^31 values
+    return round_size(per, ((i64)1 << 30) / std::max<i64>(1, (K + 1) * M), c->env.batch_round, nprob);
 }
 
 // The batched route on device pointers; any of R, Q, tt, B, ssy may be null.  PLS_HIP_ERR_ALLOC: workspace does not fit.
@@ -102,10 +93,7 @@ int fit_batch_device(pls_hip_context *c, const T *X, i64 ldx, const T *Ys, i64 l
     const double *XX = (const double *)c->xx.p;
     double *ws = (double *)c->bws.p, *Vm = (double *)c->bv.p, *Rc = Vm + KP * nround;
     double *red = (double *)c->bred.p, *msg = (double *)c->bmsg.p, *sv = (double *)c->bssy.p;
-    if (!plsk::raise_dynamic_lds((const void *)plsk::xtg_kernel<double>, (int)plsk::SyrkCfg<double>::LDS_BYTES))
-        return fail(c, PLS_HIP_ERR_DEVICE, "dynamic LDS limit of the matrix-core product could not be raised");
     const size_t cs_bytes = (size_t)A * 8;
-    const int nbk = (K + plsk::SYRK_TB - 1) / plsk::SYRK_TB;
     for (i64 b0 = 0; b0 < nprob; b0 += nround) {
         const i64 nb = std::min(nround, nprob - b0), C = nb * M, KC = (i64)K * C;
         const T *G = Ys + b0 * M * ldy;
@@ -129,15 +117,8 @@ int fit_batch_device(pls_hip_context *c, const T *X, i64 ldx, const T *Ys, i64 l
                                (const double *)msg, Lm, (const double *)Vm, Rc, KP, ws, (int)p0, K, M, A, -1, (int)c->opt_power_iters);
             LAUNCH_CHECK(c);
         }
-        const int nbc = (int)((nb + plsk::SYRK_TB - 1) / plsk::SYRK_TB);
         for (int a = 0; a < A; ++a) {
-            {   // V = XX [r_0 r_1 ...]: XX is symmetric, so this is the product XX^T Rc of xtg_kernel with one row split
-                Scope s(c, PLS_HIP_FAM_SMALL, ((i64)K * K * nbc + 2 * (i64)K * nb * nbk) * 8);
-                hipLaunchKernelGGL((plsk::xtg_kernel<double>), dim3((unsigned)(nbk * nbc), 1), dim3(256),
-                                   plsk::SyrkCfg<double>::LDS_BYTES, c->stream, XX, (i64)K, (const double *)Rc, KP, (i64)K, K, (int)nb,
-                                   nbc, (K & 1) ? 0 : 1, Vm, KP, (i64)0);
-                LAUNCH_CHECK(c);
-            }
+            CHK(launch_sym_product(c, XX, K, Rc, KP, (int)nb, Vm, KP));  // V = XX [r_0 r_1 ...]
             Scope s(c, PLS_HIP_FAM_SMALL, nb * ((i64)K * M * 3 + (i64)K * (2 * (a + 2)) + 2 * K) * 8);
             hipLaunchKernelGGL(plsk::batch_step_kernel, dim3((unsigned)nb), dim3(plsk::UPD_THREADS), cs_bytes, c->stream,
                                (const double *)nullptr, (i64)0, (const double *)Vm, Rc, KP, ws, 0, K, M, A, a, (int)c->opt_power_iters);

@@ -103,6 +103,35 @@ int compute_xx(pls_hip_context *c, const T *X, i64 ldx, i64 N, int K, double *XX
     return compute_xx_finish(c, K, XX);
 }
 
+// S (n x n, symmetric, ld n) times Rhs (n x cols, ld ldr) -> out (ld ldo): S^T Rhs = S Rhs, so this is xtg_kernel with X := S
+// and ONE row split -- no partial blocks, no reduction.  The per-component product of the batched fits (XX [r_0 r_1 ...]) and
+// of the DUAL cross-validation folds (G [Y_a(0) | Y_a(1) | ...]).
+int launch_sym_product(pls_hip_context *c, const double *S, int n, const double *Rhs, i64 ldr, int cols, double *out, i64 ldo) {
+    typedef plsk::SyrkCfg<double> Cfg;
+    if (!plsk::raise_dynamic_lds((const void *)plsk::xtg_kernel<double, false>, (int)Cfg::LDS_BYTES))
+        return fail(c, PLS_HIP_ERR_DEVICE, "dynamic LDS limit of the matrix-core product could not be raised");
+    const int nbk = (n + plsk::SYRK_TB - 1) / plsk::SYRK_TB, nbc = (cols + plsk::SYRK_TB - 1) / plsk::SYRK_TB;
+    Scope s(c, PLS_HIP_FAM_SMALL, ((i64)n * n * nbc + 2 * (i64)n * cols * nbk) * 8);
+    hipLaunchKernelGGL((plsk::xtg_kernel<double, false>), dim3((unsigned)(nbk * nbc), 1), dim3(256), Cfg::LDS_BYTES, c->stream, S, (i64)n,
+                       Rhs, ldr, (i64)n, n, cols, nbc, (n & 1) ? 0 : 1, out, ldo, (i64)0);
+    LAUNCH_CHECK(c);
+    return PLS_HIP_OK;
+}
+
+// Items (problems, folds) per round of a call that works through n of them with per_item_bytes of workspace each: as many as
+// 4 GB and half of the free device memory hold, at most value_cap (index ranges) and env_cap (> 0: the test knob).  0: not even one.
+constexpr i64 ROUND_BYTES = (i64)4 << 30;
+i64 round_size(i64 per_item_bytes, i64 value_cap, i64 env_cap, i64 n) {
+    size_t fr = 0, tot = 0;
+    if (hipMemGetInfo(&fr, &tot) != hipSuccess) {
+        (void)hipGetLastError();
+        fr = (size_t)ROUND_BYTES;
+    }
+    i64 nb = std::min<i64>(std::min<i64>(ROUND_BYTES, (i64)(fr / 2)) / per_item_bytes, value_cap);
+    if (env_cap > 0) nb = std::min<i64>(nb, env_cap);
+    return std::max<i64>(0, std::min<i64>(nb, n));
+}
+
 // Sharded fits: every rank must have derived the same bits (small_kernels.hpp, "replica guard").  Two small launches and one
 // 512-byte all-reduce per fit; the verdict lands in a host-mapped flag that pls_hip_synchronize (and the host-memory entry)
 // turn into PLS_HIP_ERR_REDUCER.

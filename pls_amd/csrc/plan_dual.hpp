@@ -25,10 +25,10 @@ template <typename T>
 int dual_gram(pls_hip_context *c, const T *X, i64 ldx, int N, int K) {
     const i64 NN = (i64)N * N, es = (i64)sizeof(T);
     // split of the sum over the columns of X: N is small, the blocks alone cannot fill the chip.  All workgroups resident at
-    // once (two per CU) when the blocks allow it; the partial blocks stay below 4 GB.
+    // once (two per CU) when the blocks allow it, no split otherwise; the partial blocks stay below 4 GB.
     const int nbn = (N + plsk::XXT_TB - 1) / plsk::XXT_TB, nblk = nbn * (nbn + 1) / 2;
     const i64 nslabs = ((i64)K + plsk::XXT_KC - 1) / plsk::XXT_KC, slots = 2 * (i64)c->num_cu;
-    i64 S = nblk <= slots ? slots / nblk : 1;
+    i64 S = plsk::row_splits(nblk, slots, 1);
     S = std::max<i64>(1, std::min<i64>(S, nslabs));
     S = std::max<i64>(1, std::min<i64>(S, ((i64)4 << 30) / (NN * 8)));
     const i64 per_split = (nslabs + S - 1) / S;
@@ -43,6 +43,17 @@ int dual_gram(pls_hip_context *c, const T *X, i64 ldx, int N, int K) {
     LAUNCH_CHECK(c);
     hipLaunchKernelGGL(plsk::xxt_reduce_kernel, dim3((unsigned)nblk, plsk::XXT_TB * plsk::XXT_TB / 256), dim3(256), 0, c->stream,
                        (const double *)part, (int)S, N, nbn, G);
+    LAUNCH_CHECK(c);
+    return PLS_HIP_OK;
+}
+
+// Z (N x cols) = G Ya, dual_gy_kernel with the fewest accumulators that hold cols <= 32 columns
+int launch_dual_gy(pls_hip_context *c, const double *G, const double *Ya, int N, int cols, double *Z) {
+    Scope s(c, PLS_HIP_FAM_SMALL, ((i64)N * N + 2 * (i64)N * cols) * 8);
+#define DUAL_GY(MT_) hipLaunchKernelGGL((plsk::dual_gy_kernel<MT_>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, c->stream, G, Ya, N, cols, Z)
+    if (cols <= 1) DUAL_GY(1); else if (cols <= 2) DUAL_GY(2); else if (cols <= 4) DUAL_GY(4); else if (cols <= 8) DUAL_GY(8);
+    else if (cols <= 16) DUAL_GY(16); else DUAL_GY(32);
+#undef DUAL_GY
     LAUNCH_CHECK(c);
     return PLS_HIP_OK;
 }
@@ -72,17 +83,9 @@ int fit_dual(pls_hip_context *c, const T *X, i64 ldx, const T *Y, i64 ldy, i64 N
                            ldy, Ya, (i64)N, N, M);
         LAUNCH_CHECK(c);
     }
-    const unsigned gy_grid = (unsigned)((N + 3) / 4);
     for (int a = 0; a < A; ++a) {
         Range r_comp("component", a);
-        {
-            Scope s(c, PLS_HIP_FAM_SMALL, (NN + 2 * (i64)N * M) * 8);
-#define DUAL_GY(MT_) hipLaunchKernelGGL((plsk::dual_gy_kernel<MT_>), dim3(gy_grid), dim3(256), 0, c->stream, (const double *)G, (const double *)Ya, N, M, Z)
-            if (M <= 1) DUAL_GY(1); else if (M <= 2) DUAL_GY(2); else if (M <= 4) DUAL_GY(4); else if (M <= 8) DUAL_GY(8);
-            else if (M <= 16) DUAL_GY(16); else DUAL_GY(32);
-#undef DUAL_GY
-            LAUNCH_CHECK(c);
-        }
+        CHK(launch_dual_gy(c, G, Ya, N, M, Z));
         {
             Scope s(c, PLS_HIP_FAM_SMALL, (i64)N * (3 * M + a + 4) * 8);
             hipLaunchKernelGGL(plsk::dual_step_kernel, dim3(1), dim3(plsk::UPD_THREADS), 0, c->stream, (const double *)Z, Ya, T64, V, Q, C,

@@ -8,8 +8,6 @@
 
 namespace {
 
-constexpr i64 DUALCV_ROUND_BYTES = (i64)4 << 30;  // workspace of one round (the rule of pls_hip_fit_batch)
-
 // the calls this route takes; every other call routes as without it
 bool cv_dual_covers(const pls_hip_context *c, i64 N, i64 M) {
     return c->opt_algo == PLS_HIP_ALGO_DUAL && !c->reducer && c->nranks == 1 && N <= plsk::DUAL_NMAX && M <= plsk::DUAL_MMAX &&
@@ -21,15 +19,8 @@ i64 cv_dual_fold_bytes(i64 N, i64 M, i64 A, i64 ts) { return (2 * N * M + N * A 
 
 // folds per round: as many as 4 GB and half of the free device memory hold (0: not even one)
 i64 cv_dual_round_size(pls_hip_context *c, i64 N, i64 M, i64 A, i64 ts, i64 num_folds) {
-    size_t fr = 0, tot = 0;
-    if (hipMemGetInfo(&fr, &tot) != hipSuccess) {
-        (void)hipGetLastError();
-        fr = (size_t)DUALCV_ROUND_BYTES;
-    }
-    i64 nb = std::min<i64>(DUALCV_ROUND_BYTES, (i64)(fr / 2)) / cv_dual_fold_bytes(N, M, A, ts);
-    nb = std::min<i64>(nb, ((i64)1 << 30) / (N * M));  // N * C of the product stays below 2^31 values
-    if (c->env.dualcv_round > 0) nb = std::min<i64>(nb, c->env.dualcv_round);
-    return std::max<i64>(0, std::min<i64>(nb, num_folds));
+    // N * C of the product stays below 2^31 values
+    return round_size(cv_dual_fold_bytes(N, M, A, ts), ((i64)1 << 30) / (N * M), c->env.dualcv_round, num_folds);
 }
 
 // X, Y device pointers, test_idx host memory, E device memory.  PLS_HIP_ERR_ALLOC: the workspace does not fit.
@@ -52,10 +43,8 @@ int cv_folds_dual(pls_hip_context *c, const T *X, i64 ldx, const T *Y, i64 ldy, 
     double *scr = ttv + nround * A, *pred = scr + nround * (N + A);
     int *pos = (int *)(pred + nround * ts * M);
     // one product kernel for the whole call: the single-wave rows of dual_gy_kernel up to 32 columns per round (the 128-wide
-    // tile of the matrix-core kernel would be mostly padding), xtg_kernel with X := G beyond
+    // tile of the matrix-core kernel would be mostly padding), xtg_kernel with X := G beyond (G is symmetric)
     const bool gy = nround * M <= 32;
-    if (!gy && !plsk::raise_dynamic_lds((const void *)plsk::xtg_kernel<double>, (int)plsk::SyrkCfg<double>::LDS_BYTES))
-        return fail(c, PLS_HIP_ERR_DEVICE, "dynamic LDS limit of the matrix-core product could not be raised");
     HIPCHK(c, hipMemcpyAsync(c->cvidx.p, test_idx, (size_t)nobs * 8, hipMemcpyHostToDevice, c->stream));
     {
         Scope s(c, PLS_HIP_FAM_SMALL, (i64)N * M * (es + 8));
@@ -63,11 +52,10 @@ int cv_folds_dual(pls_hip_context *c, const T *X, i64 ldx, const T *Y, i64 ldy, 
                            ldy, Y64, (i64)N, N, M);
         LAUNCH_CHECK(c);
     }
-    const int nbk = (N + plsk::SYRK_TB - 1) / plsk::SYRK_TB;
     for (i64 f0 = 0; f0 < num_folds; f0 += nround) {
         Range r_round("round of folds", (int)(f0 / nround));
         const i64 nb = std::min(nround, num_folds - f0);
-        const int C = (int)(nb * M), nbc = (C + plsk::SYRK_TB - 1) / plsk::SYRK_TB;
+        const int C = (int)(nb * M);
         {
             Scope s(c, PLS_HIP_FAM_SMALL, nb * ((i64)N * (2 * M + 1) + (i64)ts * (M + 1)) * 8);
             hipLaunchKernelGGL(plsk::dual_cv_init_kernel, dim3((unsigned)nb), dim3(256), 0, c->stream, (const double *)Y64,
@@ -75,19 +63,8 @@ int cv_folds_dual(pls_hip_context *c, const T *X, i64 ldx, const T *Y, i64 ldy, 
             LAUNCH_CHECK(c);
         }
         for (int a = 0; a < A; ++a) {
-            if (gy) {
-                Scope s(c, PLS_HIP_FAM_SMALL, (NN + 2 * (i64)N * C) * 8);
-#define DUALCV_GY(MT_) hipLaunchKernelGGL((plsk::dual_gy_kernel<MT_>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, c->stream, G, (const double *)Ya, N, C, Z)
-                if (C <= 1) DUALCV_GY(1); else if (C <= 2) DUALCV_GY(2); else if (C <= 4) DUALCV_GY(4); else if (C <= 8) DUALCV_GY(8);
-                else if (C <= 16) DUALCV_GY(16); else DUALCV_GY(32);
-#undef DUALCV_GY
-                LAUNCH_CHECK(c);
-            } else {  // G is symmetric, so G Y is the product G^T Y of xtg_kernel with one row split (as plan_batch.hpp's V = XX r)
-                Scope s(c, PLS_HIP_FAM_SMALL, (NN * nbc + 2 * (i64)N * C * nbk) * 8);
-                hipLaunchKernelGGL((plsk::xtg_kernel<double>), dim3((unsigned)(nbk * nbc), 1), dim3(256), plsk::SyrkCfg<double>::LDS_BYTES,
-                                   c->stream, G, (i64)N, (const double *)Ya, (i64)N, (i64)N, N, C, nbc, (N & 1) ? 0 : 1, Z, (i64)N, (i64)0);
-                LAUNCH_CHECK(c);
-            }
+            if (gy) CHK(launch_dual_gy(c, G, Ya, N, C, Z));
+            else CHK(launch_sym_product(c, G, N, Ya, (i64)N, C, Z, (i64)N));
             Scope s(c, PLS_HIP_FAM_SMALL, nb * (i64)N * (3 * M + a + 4) * 8);
             hipLaunchKernelGGL(plsk::dual_cv_step_kernel, dim3((unsigned)nb), dim3(plsk::UPD_THREADS), 0, c->stream, (const double *)Z, Ya,
                                T64, ttv, scr, (const int *)pos, pred, (const double *)Y64, E, N, M, A, a, ts, f0, nobs,

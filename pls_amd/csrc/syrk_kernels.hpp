@@ -9,17 +9,21 @@
 // padded to 34 doubles so that the MFMA operand reads (lane: column l&15, row l>>4) hit 32 distinct
 // bank pairs per half-wave.
 //
-// Workgroup = 4 waves = one 128 x 128 block of XX (each wave a 64 x 64 quadrant = 4 x 4 MFMA tiles,
-// 64 fp64 accumulators per lane); 8 operand reads feed 16 MFMAs per 4-row step.  Only blocks on or
-// above the diagonal are computed (the mirror image is written from the same accumulators).  The
-// sum over rows is split over gridDim.y workgroups per block; their partial blocks are added by
-// reduce_partials_kernel in a fixed order.
+// Workgroup = 4 waves = one 128 x 128 block of XX, computed by the block core of mfma_block.hpp.
+// Only blocks on or above the diagonal are computed (the mirror image is written from the same
+// accumulators).  The sum over rows is split over gridDim.y workgroups per block; their partial
+// blocks are added by reduce_partials_kernel in a fixed order.
+//
+// xtg_kernel<T, SYM> is this register-staged product in both of its uses: SYM = true is X^T X as
+// described (ragged N; syrk_glds8_kernel below runs whenever N % V == 0), SYM = false takes the
+// second panel from another matrix G -- the wide X^T [Y_0 | Y_1 | ...] of pls_hip_fit_batch and,
+// with X := a symmetric matrix and one row split, that plan's and the DUAL folds' per-component
+// products (launch_sym_product, plan_common.hpp).
 #pragma once
 #include "common.hpp"
+#include "mfma_block.hpp"
 
 namespace plsk {
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 constexpr int SYRK_TB = 128;  // block tile (columns of X per panel)
 // per storage type: V rows per 16-byte access, slab of RB = 16*V rows (256-byte column segments), LDS row
@@ -34,51 +38,58 @@ struct SyrkCfg {
     static constexpr size_t LDS_BYTES = 2 * (size_t)SYRK_TB * LDP * sizeof(T);
 };
 
-// blockIdx.x enumerates the nbk*(nbk+1)/2 blocks (bi <= bj); blockIdx.y = row split.
-template <typename T>
-__global__ __launch_bounds__(256, 2) void syrk_kernel(const T *__restrict__ X, i64 ldx, i64 N, int K, int nbk,
-                                                      double *__restrict__ part) {
-    constexpr int V = SyrkCfg<T>::V, SYRK_RB = SyrkCfg<T>::RB, SYRK_LDP = SyrkCfg<T>::LDP;
+// out[split][a + b * ldo] = sum over the split's rows i of X[i, a] * G[i, b]     (a < K, b < C)
+// 256 threads; dynamic LDS = SyrkCfg<T>::LDS_BYTES; blockIdx.y = row split (a contiguous range of slabs), partials pstride apart.
+// SYM = false: blockIdx.x = bi * nbc + bj, nbc = ceil(C / 128).  vec != 0: X, G are 16-byte aligned with ld % V == 0 (whole
+//              V-row packs are loaded at once); 0: element by element.
+// SYM = true:  G is X itself (ldg = ldx, C = K, nbc = ceil(K / 128); the launcher has checked the alignment, vec is not read).
+//              blockIdx.x enumerates the nbc (nbc + 1) / 2 blocks bi <= bj; a diagonal block stages one panel; the mirror
+//              block is written too; X is read once and streams past the caches (nt).
+template <typename T, bool SYM>
+__global__ __launch_bounds__(256, 2) void xtg_kernel(const T *__restrict__ X, i64 ldx, const T *__restrict__ G, i64 ldg, i64 N,
+                                                     int K, int C, int nbc, int vec, double *__restrict__ out, i64 ldo,
+                                                     i64 pstride) {
+    constexpr int V = SyrkCfg<T>::V, RB = SyrkCfg<T>::RB, LDP = SyrkCfg<T>::LDP;
     extern __shared__ __attribute__((aligned(16))) unsigned char slab_raw[];  // As[TB][LDP], Bs[TB][LDP]
-    T *As = reinterpret_cast<T *>(slab_raw), *Bs = As + SYRK_TB * SYRK_LDP;
+    T *As = reinterpret_cast<T *>(slab_raw), *Bs = As + SYRK_TB * LDP;
 
-    int bi = 0, rem = blockIdx.x;
-    while (rem >= nbk - bi) { rem -= nbk - bi; ++bi; }
-    const int bj = bi + rem;
-    const bool diag = (bi == bj);
+    int bi, bj;
+    if constexpr (SYM) {
+        tri_block(blockIdx.x, nbc, bi, bj);
+    } else {
+        bi = blockIdx.x / nbc, bj = blockIdx.x % nbc;
+    }
+    const bool diag = SYM && bi == bj;
     if (diag) Bs = As;
 
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    // staging map: row group rp (16 of them, V rows each), column group cgi (16 of them); 8 columns per thread
-    const int rp = tid & 15, cgi = tid >> 4;
-    // compute map
-    const int a0 = (wv >> 1) * 64, b0 = (wv & 1) * 64;
-    const int li = lane & 15, lq = lane >> 4;
-
+    // staging map: row group rp (16 of them, V rows each), column group cgi (16 of them); 8 columns per thread and panel
+    const int rp = threadIdx.x & 15, cgi = threadIdx.x >> 4;
+    const QuadMap q;
     f64x4 acc[4][4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int n = 0; n < 4; ++n) acc[m][n] = f64x4{0.0, 0.0, 0.0, 0.0};
+    quad_zero(acc);
 
-    const i64 nslabs = (N + SYRK_RB - 1) / SYRK_RB;
+    const i64 nslabs = (N + RB - 1) / RB;
     Pack<T, V> ga[8], gb[8];
 
+    auto ld = [](const T *p) {
+        if constexpr (SYM) return ld_pack_nt<T, V>(p);
+        else return ld_pack<T, V>(p);
+    };
     auto load_slab = [&](i64 s) {
-        const i64 r0 = s * SYRK_RB + V * rp;
+        const i64 r0 = s * RB + V * rp;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int ca = bi * SYRK_TB + cgi + 16 * j, cb = bj * SYRK_TB + cgi + 16 * j;
 #pragma unroll
             for (int e = 0; e < V; ++e) ga[j].v[e] = gb[j].v[e] = (T)0;
-            if (r0 + V <= N) {
-                if (ca < K) ga[j] = ld_pack_nt<T, V>(X + r0 + (i64)ca * ldx);
-                if (!diag && cb < K) gb[j] = ld_pack_nt<T, V>(X + r0 + (i64)cb * ldx);
-            } else if (r0 < N) {  // ragged last rows: element-wise, the missing slots stay zero
+            if ((SYM || vec) && r0 + V <= N) {
+                if (ca < K) ga[j] = ld(X + r0 + (i64)ca * ldx);
+                if (!diag && cb < C) gb[j] = ld(G + r0 + (i64)cb * ldg);
+            } else if (r0 < N) {  // ragged last rows, unaligned layouts: element-wise, the missing slots stay zero
                 for (int e = 0; e < V; ++e)
                     if (r0 + e < N) {
                         if (ca < K) ga[j].v[e] = X[r0 + e + (i64)ca * ldx];
-                        if (!diag && cb < K) gb[j].v[e] = X[r0 + e + (i64)cb * ldx];
+                        if (!diag && cb < C) gb[j].v[e] = G[r0 + e + (i64)cb * ldg];
                     }
             }
         }
@@ -90,9 +101,9 @@ __global__ __launch_bounds__(256, 2) void syrk_kernel(const T *__restrict__ X, i
             constexpr int H = 8 / sizeof(T);  // elements per 8-byte piece
 #pragma unroll
             for (int e = 0; e < V; e += H) {
-                *reinterpret_cast<Pack<T, H> *>(As + c * SYRK_LDP + V * rp + e) = *reinterpret_cast<const Pack<T, H> *>(&ga[j].v[e]);
+                *reinterpret_cast<Pack<T, H> *>(As + c * LDP + V * rp + e) = *reinterpret_cast<const Pack<T, H> *>(&ga[j].v[e]);
                 if (!diag)
-                    *reinterpret_cast<Pack<T, H> *>(Bs + c * SYRK_LDP + V * rp + e) = *reinterpret_cast<const Pack<T, H> *>(&gb[j].v[e]);
+                    *reinterpret_cast<Pack<T, H> *>(Bs + c * LDP + V * rp + e) = *reinterpret_cast<const Pack<T, H> *>(&gb[j].v[e]);
             }
         }
     };
@@ -109,36 +120,10 @@ __global__ __launch_bounds__(256, 2) void syrk_kernel(const T *__restrict__ X, i
         store_slab();
         __syncthreads();
 #pragma unroll
-        for (int kk = 0; kk < SYRK_RB; kk += 4) {
-            double a[4], b[4];
-#pragma unroll
-            for (int m = 0; m < 4; ++m) a[m] = (double)As[(a0 + 16 * m + li) * SYRK_LDP + kk + lq];
-#pragma unroll
-            for (int n = 0; n < 4; ++n) b[n] = (double)Bs[(b0 + 16 * n + li) * SYRK_LDP + kk + lq];
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-#pragma unroll
-                for (int n = 0; n < 4; ++n)
-                    acc[m][n] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[m], b[n], acc[m][n], 0, 0, 0);
-        }
+        for (int kk = 0; kk < RB; kk += 4) quad_step<LDP, 1>(As, Bs, q, kk, acc);
     }
-
-    // f64 C/D layout: lane holds D[row = (lane>>4) + 4*reg][col = lane&15]; row <-> a, col <-> b
-    double *out = part + (i64)blockIdx.y * ((i64)K * K);
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int n = 0; n < 4; ++n)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int ga_ = bi * SYRK_TB + a0 + 16 * m + lq + 4 * r;
-                const int gb_ = bj * SYRK_TB + b0 + 16 * n + li;
-                if (ga_ < K && gb_ < K) {
-                    const double v = acc[m][n][r];
-                    out[ga_ + (i64)gb_ * K] = v;
-                    if (!diag) out[gb_ + (i64)ga_ * K] = v;  // the mirror block
-                }
-            }
+    // row <-> column of X, col <-> column of G
+    quad_store(acc, q, out + (i64)blockIdx.y * pstride, ldo, bi * SYRK_TB, bj * SYRK_TB, K, C, SYM && !diag);
 }
 
 // 16 bytes per lane, global -> LDS without a register destination: lane l's bytes land at lds_base + 16 l
@@ -154,7 +139,7 @@ __device__ __forceinline__ void glds16(const void *gsrc, void *lds_base) {
 #endif
 }
 
-// ---- LDS-DMA variant (the kernel that runs whenever N % V == 0; the register-staged one above takes ragged N) ----------
+// ---- LDS-DMA variant (the kernel that runs whenever N % V == 0; xtg_kernel<T, true> above takes ragged N) ----------------
 // The register-staged kernel above exposes the global-load latency of every slab (load -> barrier -> LDS
 // store -> barrier -> 128 MFMAs; only the second workgroup of the CU covers it): 67-68 % MFMA-busy.  Here
 // the panels go global -> LDS directly (global_load_lds_dwordx4: no staging registers),
@@ -700,11 +685,8 @@ int launch_syrk(hipStream_t stream, int num_cu, const T *X, i64 ldx, i64 N, int 
     const int nbk = (K + SYRK_TB - 1) / SYRK_TB;
     const int nblocks = nbk * (nbk + 1) / 2;
     const i64 nslabs = (N + SYRK_RB - 1) / SYRK_RB;
-    // Row split: all workgroups resident at once (2 per CU) when the blocks allow it -- a grid that is
-    // one workgroup over a residency wave takes twice as long (measured: 520 workgroups 10.0 ms, 510
-    // workgroups 6.5 ms) -- otherwise at least ~8 waves so that the tail is small.
     const i64 slots = 2 * (i64)num_cu;
-    i64 S = nblocks <= slots ? slots / nblocks : (8 * slots + nblocks - 1) / nblocks;
+    i64 S = row_splits(nblocks, slots, 8);
     S = std::max<i64>(1, std::min<i64>(S, nslabs));
     S = std::min<i64>(S, part_capacity_doubles / ((i64)K * K));
     if (S < 1) return 1;
@@ -762,9 +744,9 @@ int launch_syrk(hipStream_t stream, int num_cu, const T *X, i64 ldx, i64 N, int 
         *nb = (int)nslots;
         return 0;
     }
-    if (!raise_dynamic_lds(reinterpret_cast<const void *>(&syrk_kernel<T>), (int)SYRK_LDS_BYTES)) return 1;
-    hipLaunchKernelGGL(syrk_kernel<T>, dim3(nblocks, (unsigned)S), dim3(256), SYRK_LDS_BYTES, stream, X, ldx, N, K, nbk,
-                       part);
+    if (!raise_dynamic_lds(reinterpret_cast<const void *>(&xtg_kernel<T, true>), (int)SYRK_LDS_BYTES)) return 1;
+    hipLaunchKernelGGL((xtg_kernel<T, true>), dim3(nblocks, (unsigned)S), dim3(256), SYRK_LDS_BYTES, stream, X, ldx, X, ldx, N, K, K,
+                       nbk, 1, part, (i64)K, (i64)K * K);
     *nb = (int)S;
     return 0;
 }

@@ -373,6 +373,10 @@ FIT_CASES = [
     ("defer4", 4098, 512, 1, 7, "f64", "aligned", {"PLS_HIP_RESIDENT": 0}, {"ALGO": 1, "DEFER": 4}),
     ("gram", 3001, 64, 2, 6, "f64", "eigen", {"PLS_HIP_RESIDENT": 0}, {"ALGO": 2}),
     ("gram-f32", 5004, 200, 3, 5, "f32", "aligned", {"PLS_HIP_RESIDENT": 0}, {"ALGO": 2}),
+    # (16-byte columns, N ragged for either row pack: the register-staged X^T X -- a diagonal block, an off-diagonal block with
+    # its mirror, a ragged second diagonal block; three column blocks in fp32)
+    ("gram-ragged-rows", 2051, 130, 2, 5, "f64", "aligned", {"PLS_HIP_RESIDENT": 0}, {"ALGO": 2}),
+    ("gram-ragged-rows-f32", 2051, 300, 2, 5, "f32", "aligned", {"PLS_HIP_RESIDENT": 0}, {"ALGO": 2}),
     ("resident", 5000, 128, 1, 10, "f64", "aligned", {}, {}),
     ("resident-m5-f32", 3001, 77, 5, 7, "f32", "eigen", {}, {}),
     ("resident-gram", 5003, 128, 1, 11, "f64", "eigen", {}, {"ALGO": 3}),
