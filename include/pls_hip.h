@@ -94,7 +94,8 @@ typedef enum { PLS_HIP_MEM_HOST = 0, PLS_HIP_MEM_DEVICE = 1 } pls_hip_mem;
  *           PLS_HIP_OPT_GRAPH, it simply runs.  Like GRAM it squares the singular values of X; unlike GRAM it
  *           orthogonalises every score against the earlier ones explicitly.
  *           pls_hip_cv_folds on a handle with this option runs every fold from the same G: one sweep over X for the whole
- *           call (see there). */
+ *           call (see there).  pls_hip_fit_batch on such a handle runs every problem from the same G: one sweep over X for
+ *           Q, tt and ssy, one wide product X^T [...] per round for R and for B, any K (see there). */
 typedef enum {
     PLS_HIP_ALGO_KERNEL = 0,
     PLS_HIP_ALGO_NIPALS = 1,
@@ -390,6 +391,20 @@ PLS_HIP_API int pls_hip_x_diagnostics(pls_hip_handle h, const void *X, int64_t l
  * Per-problem route (every other shape, a workspace that does not fit, or PLS_HIP_BATCH_REFIT=1 in the environment): one
  * KERNEL_TYPE2 fit per problem under the handle's plan -- same results to rounding, nprob fits; shapes pls_hip_fit refuses
  * return its status.
+ * Under PLS_HIP_ALGO_DUAL (no reducer, 1 <= N <= 8192, M <= 32, PLS_HIP_BATCH_REFIT unset) the call is taken before both by the
+ * sample-space route: G = X X^T once -- with Q, tt and ssy asked for the only pass over X, whatever A and nprob are -- then
+ * every problem runs the plan's recursion on vectors of length N from its own Y_b, in rounds of as many problems as 4 GB of
+ * workspace and half of the free device memory hold (2 N M + 2 N A + A^2 + M A + 2 A + N values per problem;
+ * PLS_HIP_DUALBATCH_ROUND=n caps a round): per component one product G [Y_a of every problem] and one workgroup per problem.
+ * Q, tt (= t_a^T t_a) and ssy are written from N-sized work.  R and B come back through sample space: R_b = X^T S_b with
+ * s_a = u_a - sum_{j<a} C[j,a] s_j, B_b = X^T (S_b Q_b^T), so R (and B) of all problems of a round is ONE product
+ * X^T [S_0 | S_1 | ...] written straight into the caller's array: one launch per round and output (up to 64 columns the
+ * back-projection kernel of the DUAL fit, beyond them 128 x 128 blocks on the matrix cores), nothing K-sized besides the
+ * outputs.  Any K, any ld >= N, element-aligned pointers, either storage type (fp64 arithmetic), either memory kind; the
+ * same values as the other routes to rounding (for M > 1 a component's sign may differ, as for the DUAL fit; B does not
+ * depend on it); two calls with the same arguments return the same bits.  A call outside those limits routes exactly as
+ * without the option, and so does one whose workspace does not fit even for one problem.  PLS_HIP_BATCH_REFIT=1 under the
+ * option is the library's cross-check for K <= 32768.
  * Row-sharded handle (a reducer installed): a COLLECTIVE with the same K, M, A, nprob on every rank; Ys holds the rank's
  * own rows.  X^T X and the products of every piece of problems are summed over the ranks (pls_hip_allreduce_fn lists the
  * messages), the component loops then run replicated from identical bits: every rank ends with identical outputs.
@@ -508,7 +523,8 @@ PLS_HIP_API int pls_hip_group_x_diagnostics(pls_hip_group g, pls_hip_matrix X, i
                                             const double *tvar, pls_hip_matrix Qres, pls_hip_matrix T2, pls_hip_matrix S,
                                             double *ssx, double *sst);
 /* pls_hip_fit_batch on resident X (N x K) and Ys (N x nprob*M, the storage type of X); R, Q, tt, B, ssy HOST, any may be NULL.
- * The members run as for pls_hip_group_fit; an X^T X that came with pls_hip_group_upload_xy is used. */
+ * The members run as for pls_hip_group_fit; an X^T X that came with pls_hip_group_upload_xy is used.  A one-member group
+ * whose member has PLS_HIP_ALGO_DUAL set reaches the sample-space route of pls_hip_fit_batch through the member's handle. */
 PLS_HIP_API int pls_hip_group_fit_batch(pls_hip_group g, pls_hip_matrix X, pls_hip_matrix Ys, int64_t M, int64_t A,
                                         double *R, double *Q, double *tt, double *B, double *ssy);
 /* pls_hip_cv_folds on resident data, E (M x nobs x A) HOST.  Groups of one member only (the fold kernel works on

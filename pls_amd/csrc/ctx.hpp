@@ -36,6 +36,7 @@ struct pls_hip_context {
     DevBuf bws, bv, bred, bmsg, bssy, bY, boR, boQ, bott, boB, bossy;  // pls_hip_fit_batch (plan_batch.hpp): per-problem workspace, V and r columns, the sliced product, the message, host staging
     DevBuf dG, dpart, dV, dT, dY, dZ, dC, dscr;  // PLS_HIP_ALGO_DUAL (plan_dual.hpp): X X^T, its split partials, [U | T / tt], the fp64 scores, Y_a, G Y_a, C, small vectors
     DevBuf dcv;  // its cross-validation folds (plan_dual_cv.hpp): the state of a round's folds
+    DevBuf dbat;  // its batched fits (plan_dual_batch.hpp): the state of a round's problems
     i64 opt_val_lds_rows = -1;  // PLS_HIP_OPT_VALIDATION_LDS_ROWS; -1 = the device's own limit
     i64 val_lds_rows_dev = -1;  // that limit, found on first use
     std::string err;
@@ -91,6 +92,9 @@ struct pls_hip_context {
     //   PLS_HIP_BATCH_REFIT=1    pls_hip_fit_batch as one KERNEL_TYPE2 fit per problem (the general form; tests compare)
     //   PLS_HIP_BATCH_ROUND=n    at most n problems per round of pls_hip_fit_batch's batched route (tests: several rounds)
     //   PLS_HIP_DUALCV_ROUND=n   at most n folds per round of pls_hip_cv_folds under PLS_HIP_ALGO_DUAL (tests: several rounds)
+    //   PLS_HIP_DUALBATCH_ROUND=n  at most n problems per round of pls_hip_fit_batch under PLS_HIP_ALGO_DUAL (tests: several rounds)
+    //   PLS_HIP_DUALBATCH_SWEEPS=1 its back-projection beyond 64 columns as one sweep of dual_xtv_kernel per 64 columns instead
+    //                            of one launch of dual_xtvb_kernel (A/B measurements; tests compare)
     //   PLS_HIP_RESIDENT=0       mid-size single-response fits on the general plan instead of the one-launch resident fit
     //   PLS_HIP_REPLICA_GUARD=0  no replica-divergence check after a sharded fit (must be the same on every rank)
     //   PLS_HIP_TURNAROUND=0     every fused pass walks ascending with the nt policy throughout (A/B measurements; must be the
@@ -101,6 +105,8 @@ struct pls_hip_context {
         bool batch_refit = false;
         i64 batch_round = 0;
         i64 dualcv_round = 0;
+        i64 dualbatch_round = 0;
+        bool dualbatch_sweeps = false;
         bool tiny = true, cv_refit = false, tail = true, replica_guard = true, resident = true;
         int tail_update = 1;  // 0: never, 1: in the tail of READ-ONLY passes (default), 2: of every pass
         int xb4 = 1;          // PLS_HIP_XB4=0: X B with 5..32 columns on the older kernels

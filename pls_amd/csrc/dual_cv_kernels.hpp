@@ -10,7 +10,7 @@
 //   dual_cv_init_kernel   per fold of a round: the position of every row in the fold's test set (-1: a training row),
 //                         Y_0 = diag(m) Y, the running predictions of the held-out rows = 0
 //   dual_cv_step_kernel   one component of every fold of the round, one workgroup per fold: the body of dual_step_kernel
-//                         with the mask (dual_step_body<true>, dual_kernels.hpp), plus the predictions of the held-out rows
+//                         with the mask (dual_step_body<DUAL_CV>, dual_kernels.hpp), plus the predictions of the held-out rows
 //                         and column a of E
 // The round's product Z = G [Y_a(0) | Y_a(1) | ...] between them is xtg_kernel<double, false> with X := G (launch_sym_product)
 // or, for at most 32 columns, dual_gy_kernel.  Every sum is taken in a fixed order; nothing waits on another workgroup.
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(UPD_THREADS) void dual_cv_step_kernel(const double 
                                                                    double *__restrict__ predall, const double *__restrict__ Y64,
                                                                    double *__restrict__ E, int N, int M, int A, int a, int ts,
                                                                    i64 fold0, i64 nobs, int power_iters) {
-    dual_step_body<true>(Zall, Yall, Tall, ttall, scrall, N, M, A, a, power_iters, nullptr, nullptr, nullptr, posall, predall, Y64, E,
+    dual_step_body<DUAL_CV>(Zall, Yall, Tall, ttall, scrall, N, M, A, a, power_iters, nullptr, nullptr, nullptr, posall, predall, Y64, E,
                          ts, fold0, nobs);
 }
 

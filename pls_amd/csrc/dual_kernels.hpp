@@ -7,7 +7,8 @@
 //   dual_gy_kernel        Z = G Y_a (N x M): one wave per column of the symmetric G, the whole chip
 //   dual_step_kernel      everything else of a component, N (M + a) work, ONE workgroup: direction, norm, orthogonalisation
 //                         of the score against the earlier ones, loading of Y, deflation of Y_a (dual_step_body, which the
-//                         cross-validation folds of dual_cv_kernels.hpp run with their training-row masks)
+//                         cross-validation folds of dual_cv_kernels.hpp run with their training-row masks and the batched fits
+//                         of dual_batch_kernels.hpp per problem)
 //   dual_xtv_kernel       [W | P] = X^T [U | T diag(1/tt)], up to 64 columns per sweep over X, on the matrix cores
 //   dual_r_kernel         r_a = w_a - sum_{j<a} C[j, a] r_j, a thread per row of R
 //   dual_convert_kernel   Y -> fp64 working copy, fp64 scores -> T in the storage type
@@ -123,16 +124,20 @@ __global__ __launch_bounds__(256) void dual_gy_kernel(const double *__restrict__
 //               u = Y_a q^, g = Z q^
 //   nw = sqrt(u^T g) = |X^T u| (:411);  c_j = t_j^T g / tt_j, t = (g - sum_j c_j t_j) / nw (the t = X r of :419);
 //   tt = t^T t, q = Y_a^T t / tt (:428), Y_a -= t q^T
-// CV = false, the fit (dual_step_kernel): also stores C[j, a] = c_j / nw = p_j^T w_a, V[:, a] = u / nw, V[:, A + a] = t / tt
+// MODE = DUAL_FIT, the fit (dual_step_kernel): also stores C[j, a] = c_j / nw = p_j^T w_a, V[:, a] = u / nw, V[:, A + a] = t / tt
 // and Q[:, a].
-// CV = true, fold blockIdx.x of a round of cross-validation folds (dual_cv_step_kernel, fold fold0 + blockIdx.x of the
+// MODE = DUAL_CV, fold blockIdx.x of a round of cross-validation folds (dual_cv_step_kernel, fold fold0 + blockIdx.x of the
 // call): the fold's slice of every array -- Ya, Z (N x M), T64 (N x A), ttv (A), scr (N + A), pos (N), pred (ts x M) -- and
 // the 0/1 mask of its training rows (pos < 0; dual_cv_kernels.hpp has the algebra):
 //   c_j and tt sum over the training rows only; t is formed and stored for every row;
 //   Y_a is deflated on the training rows; on a held-out row i of the fold pred[i, m] += t q_m and
 //   E[m][fold * ts + i, a] = Y[row, m] - pred[i, m] (E: M matrices of nobs x A, column-major).
+// MODE = DUAL_BATCH, problem blockIdx.x of a round of pls_hip_fit_batch (dual_batch_step_kernel, dual_batch_kernels.hpp): the
+// fit's step, no mask, on the problem's slice of every array -- Ya, Z (N x M), T64, V (N x A: U only), C (A x A), Q (M x A),
+// ttv (A), scr (N + A).
 // Stores T64[:, a] = t and ttv[a].  scr: N + A doubles (g, then c).
-template <bool CV>
+enum { DUAL_FIT = 0, DUAL_CV = 1, DUAL_BATCH = 2 };
+template <int MODE>
 __device__ __forceinline__ void dual_step_body(const double *__restrict__ Zall, double *__restrict__ Yall, double *__restrict__ Tall,
                                                double *__restrict__ ttall, double *__restrict__ scrall, int N, int M, int A, int a,
                                                int power_iters, double *__restrict__ V, double *__restrict__ Q,
@@ -140,12 +145,18 @@ __device__ __forceinline__ void dual_step_body(const double *__restrict__ Zall, 
                                                const double *__restrict__ Y64, double *__restrict__ E, int ts, i64 fold0, i64 nobs) {
     __shared__ UpdShared sh;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const i64 f = CV ? blockIdx.x : 0;
+    constexpr bool CV = MODE == DUAL_CV;
+    const i64 f = MODE != DUAL_FIT ? blockIdx.x : 0;
     const double *Z = Zall + f * M * N;
     double *Ya = Yall + f * M * N, *T64 = Tall + f * (i64)N * A, *ttv = ttall + f * A;
     double *gbuf = scrall + f * (N + A), *cbuf = gbuf + N;
-    const int *pos = posall + f * N;
-    double *pred = predall + f * ts * M;
+    const int *pos = CV ? posall + f * N : nullptr;
+    double *pred = CV ? predall + f * ts * M : nullptr;
+    if constexpr (MODE == DUAL_BATCH) {
+        V += f * N * A;
+        Q += f * M * A;
+        C += f * A * A;
+    }
     double u[DUAL_RPT], g[DUAL_RPT], t[DUAL_RPT];
     int ps[DUAL_RPT];  // (CV) the row's position in the fold's test set, -1: a training row
     if (M > 1) {
@@ -226,7 +237,7 @@ __device__ __forceinline__ void dual_step_body(const double *__restrict__ Zall, 
             for (int m = 0; m < M; ++m) Ya[n + (i64)m * N] = fma(-t[i], sh.qs[m], Ya[n + (i64)m * N]);
             if constexpr (!CV) {
                 V[n + (i64)a * N] = u[i] / nw;
-                V[n + (i64)(A + a) * N] = t[i] / tt;
+                if constexpr (MODE == DUAL_FIT) V[n + (i64)(A + a) * N] = t[i] / tt;
             }
         } else {
             double *e = E + (i64)a * nobs + (fold0 + f) * ts + ps[i];
@@ -244,7 +255,7 @@ __global__ __launch_bounds__(UPD_THREADS) void dual_step_kernel(const double *__
                                                                 double *__restrict__ Q, double *__restrict__ C,
                                                                 double *__restrict__ ttv, double *__restrict__ scr, int N, int M,
                                                                 int A, int a, int power_iters) {
-    dual_step_body<false>(Z, Ya, T64, ttv, scr, N, M, A, a, power_iters, V, Q, C, nullptr, nullptr, nullptr, nullptr, 0, 0, 0);
+    dual_step_body<DUAL_FIT>(Z, Ya, T64, ttv, scr, N, M, A, a, power_iters, V, Q, C, nullptr, nullptr, nullptr, nullptr, 0, 0, 0);
 }
 
 constexpr int XTV_KB = 64;   // columns of X per workgroup

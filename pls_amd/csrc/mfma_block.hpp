@@ -1,6 +1,6 @@
 // mfma_block.hpp -- the 128 x 128 block product on v_mfma_f64_16x16x4_f64 that xtg_kernel (syrk_kernels.hpp: X^T X and
-// X^T G) and xxt_kernel (dual_kernels.hpp: X X^T) share.  Each kernel stages its own two panels into LDS; from there on
-// the work is the same:
+// X^T G), xxt_kernel (dual_kernels.hpp: X X^T) and dual_xtvb_kernel (dual_batch_kernels.hpp: X^T V, V fp64) share.  Each kernel
+// stages its own two panels into LDS; from there on the work is the same:
 //   workgroup = 4 waves, wave (wv >> 1, wv & 1) owns a 64 x 64 quadrant = 4 x 4 MFMA tiles, 64 fp64 accumulators per lane;
 //   a step of 4 contraction indices is 8 operand reads (lane l: row l & 15 of a tile, index l >> 4) and 16 MFMAs;
 //   lane l leaves with D[row (l >> 4) + 4 reg][col l & 15] of every tile.
@@ -66,6 +66,22 @@ __device__ __forceinline__ void quad_store(const f64x4 (&acc)[4][4], const QuadM
                     out[gi + (i64)gj * ldo] = v;
                     if (mirror) out[gj + (i64)gi * ldo] = v;
                 }
+            }
+}
+
+// the transposed block: out[gj + gi * ldo] for gi < ilim, gj < jlim.  The 16 lanes of a tile row store 16 consecutive entries
+// of an output column (128 bytes), where quad_store leaves 4: for a product whose B panel runs along the output's rows
+__device__ __forceinline__ void quad_store_t(const f64x4 (&acc)[4][4], const QuadMap &q, double *__restrict__ out, i64 ldo, int i0,
+                                             i64 j0, int ilim, i64 jlim) {
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int n = 0; n < 4; ++n)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int gi = i0 + q.a0 + 16 * m + q.lq + 4 * r;
+                const i64 gj = j0 + q.b0 + 16 * n + q.li;
+                if (gi < ilim && gj < jlim) out[gj + (i64)gi * ldo] = acc[m][n][r];
             }
 }
 

@@ -1,4 +1,5 @@
-// plan_batch.hpp -- pls_hip_fit_batch: many response sets against one X.  The batched route (X^T X once, the wide X^T [Y_0 | Y_1 | ...]
+// plan_batch.hpp -- pls_hip_fit_batch: many response sets against one X.  The sample-space route of plan_dual_batch.hpp under
+// PLS_HIP_ALGO_DUAL; otherwise the batched route (X^T X once, the wide X^T [Y_0 | Y_1 | ...]
 // on the matrix cores, two launches per component for all problems of a round) and the per-problem route (one KERNEL_TYPE2 fit each).
 // Part of libpls_hip.so: included by pls_hip.hip (one translation unit), in the order given there.
 #pragma once
@@ -205,7 +206,17 @@ int fit_batch_impl(pls_hip_context *h, const void *X, i64 ldx, const void *Ys, i
         dssy = ssy ? (double *)h->bossy.p : nullptr;
     }
     int rc = PLS_HIP_ERR_ALLOC;
-    const bool batched = batch_covers(h, K, M, A);
+    if (batch_dual_covers(h, N, M)) {  // the sample-space plan, an explicit opt-in: every problem from one X X^T
+        if (dtype == PLS_HIP_F64)
+            rc = fit_batch_dual<double>(h, (const double *)dX, dldx, (const double *)dY, dldy, (int)N, K, (int)M, (int)A, nprob, dR, dQ,
+                                        dtt, dB, dssy);
+        else
+            rc = fit_batch_dual<float>(h, (const float *)dX, dldx, (const float *)dY, dldy, (int)N, K, (int)M, (int)A, nprob, dR, dQ,
+                                       dtt, dB, dssy);
+        if (rc == PLS_HIP_ERR_ALLOC) h->err.clear();  // its workspace does not fit: the routes below
+    }
+    const bool dual = rc != PLS_HIP_ERR_ALLOC;  // (the sample-space route took the call)
+    const bool batched = !dual && batch_covers(h, K, M, A);
     if (batched) {
         if (dtype == PLS_HIP_F64)
             rc = fit_batch_device<double>(h, (const double *)dX, dldx, (const double *)dY, dldy, N, (int)K, (int)M, (int)A, nprob, dR,
@@ -215,7 +226,7 @@ int fit_batch_impl(pls_hip_context *h, const void *X, i64 ldx, const void *Ys, i
                                          dtt, dB, dssy);
     }
     // declined, or (single rank: the ranks of a sharded handle must not differ in their route) no room for the batched workspace
-    if (!batched || (rc == PLS_HIP_ERR_ALLOC && !h->reducer)) {
+    if (!dual && (!batched || (rc == PLS_HIP_ERR_ALLOC && !h->reducer))) {
         h->err.clear();
         if (M > plsk::LM_MAX || K > 32768)
             return fail(h, PLS_HIP_ERR_UNSUPPORTED, "fit_batch: the per-problem route is pls_hip_fit's: M <= 1024, K <= 32768");

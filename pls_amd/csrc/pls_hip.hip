@@ -36,6 +36,7 @@
 #include "batch_kernels.hpp"
 #include "dual_kernels.hpp"
 #include "dual_cv_kernels.hpp"
+#include "dual_batch_kernels.hpp"
 #include "synth_kernels.hpp"
 #include "host_pipeline.hpp"
 #include "exchange_kernels.hpp"
@@ -95,6 +96,8 @@ int pls_hip_create(pls_hip_handle *out, int device, void *stream) {
         c->env.batch_refit = on("PLS_HIP_BATCH_REFIT");
         if (const char *e = getenv("PLS_HIP_BATCH_ROUND")) c->env.batch_round = atoll(e);
         if (const char *e = getenv("PLS_HIP_DUALCV_ROUND")) c->env.dualcv_round = atoll(e);
+        if (const char *e = getenv("PLS_HIP_DUALBATCH_ROUND")) c->env.dualbatch_round = atoll(e);
+        c->env.dualbatch_sweeps = on("PLS_HIP_DUALBATCH_SWEEPS");
         c->env.tail = !off("PLS_HIP_TAIL");
         {
             const char *e = getenv("PLS_HIP_TAIL");
@@ -126,7 +129,7 @@ int pls_hip_destroy(pls_hip_handle h) {
                       &h->hT, &h->hW, &h->hP, &h->hQ, &h->hR, &h->hB, &h->hIn, &h->hOut, &h->valout, &h->valpart, &h->vale, &h->valacc, &h->valkeys,
                       &h->valhist, &h->xdS, &h->xdQ, &h->xdPT, &h->xdred, &h->xdtv, &h->xdoQ, &h->xdoT, &h->xdoS, &h->xdsmall,
                       &h->bws, &h->bv, &h->bred, &h->bmsg, &h->bssy, &h->bY, &h->boR, &h->boQ, &h->bott, &h->boB, &h->bossy,
-                      &h->dG, &h->dpart, &h->dV, &h->dT, &h->dY, &h->dZ, &h->dC, &h->dscr, &h->dcv};
+                      &h->dG, &h->dpart, &h->dV, &h->dT, &h->dY, &h->dZ, &h->dC, &h->dscr, &h->dcv, &h->dbat};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (void *q : h->graveyard) (void)hipFree(q);
@@ -534,6 +537,7 @@ int pls_hip_sse_by_components(pls_hip_handle h, const void *S, int64_t lds, cons
 
 #include "plan_cv.hpp"
 #include "plan_dual_cv.hpp"
+#include "plan_dual_batch.hpp"
 #include "plan_batch.hpp"
 
 

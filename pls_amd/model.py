@@ -465,6 +465,8 @@ class Handle:
         outputs `want` names: "R" (nprob, K, A), "Q" (nprob, M, A), "tt" (nprob, A), "B" (nprob, K, M), "ssy" (nprob, M) --
         torch tensors on the device of X for torch inputs (the call only enqueues), numpy arrays for numpy inputs.
         W, P and T are not available here: fit one problem with fit_device / fit_host for those.
+        With OPT_ALGO = ALGO_DUAL (no reducer, N <= 8192, M <= 32) every problem runs from one X X^T instead: any K, one sweep
+        over X for Q, tt and ssy, one wide product per output for R and B.
         Row-sharded handle: a collective, X and Ys the rank's own rows; every rank receives identical outputs."""
         want = _batch_want(want)
         if _is_torch(X):
