@@ -144,18 +144,16 @@ int launch_update(pls_hip_context *c, double *red, double *XY, double *W, double
         double *gp = (double *)c->wide1.p, *cp = gp + (i64)plsk::WM_GSTRIDE * w1g, *qp = cp + (i64)A * w1g;
         const dim3 g(w1g), b(plsk::W1_WG);
         Scope s(c, PLS_HIP_FAM_SMALL, ((i64)K * M * 3 + (i64)K * (2 * (a + 2)) + K) * 8);
-#define WM_CASE(MM_)                                                                                                              \
-    do {                                                                                                                          \
-        hipLaunchKernelGGL((plsk::widem_a_kernel<MM_>), g, b, 0, c->stream, red, XY, P, Q, K, M, A, a, w1e, (const double *)qp, gp);  \
-        if (n < A) {                                                                                                              \
-            hipLaunchKernelGGL((plsk::widem_b_kernel<MM_>), g, b, (size_t)plsk::W1_WG * w1e * 8, c->stream, (const double *)XY, W,      \
-                               (const double *)P, K, M, n, w1e, (int)c->opt_power_iters, (const double *)gp, cp);                  \
-            hipLaunchKernelGGL((plsk::widem_c_kernel<MM_>), g, b, (size_t)(n + 1) * 8, c->stream, (const double *)XY,                  \
-                               (const double *)W, R, v, K, M, n, w1e, nip, (const double *)cp, qp);                                \
-        }                                                                                                                         \
-    } while (0)
-        if (M <= 2) WM_CASE(2); else if (M <= 4) WM_CASE(4); else WM_CASE(8);
-#undef WM_CASE
+        with_mm(M, [&](auto mm) {
+            constexpr int MM = decltype(mm)::value;
+            hipLaunchKernelGGL((plsk::widem_a_kernel<MM>), g, b, 0, c->stream, red, XY, P, Q, K, M, A, a, w1e, (const double *)qp, gp);
+            if (n < A) {
+                hipLaunchKernelGGL((plsk::widem_b_kernel<MM>), g, b, (size_t)plsk::W1_WG * w1e * 8, c->stream, (const double *)XY, W,
+                                   (const double *)P, K, M, n, w1e, (int)c->opt_power_iters, (const double *)gp, cp);
+                hipLaunchKernelGGL((plsk::widem_c_kernel<MM>), g, b, (size_t)(n + 1) * 8, c->stream, (const double *)XY,
+                                   (const double *)W, R, v, K, M, n, w1e, nip, (const double *)cp, qp);
+            }
+        });
         LAUNCH_CHECK(c);
         return PLS_HIP_OK;
     }
@@ -173,10 +171,10 @@ int launch_update(pls_hip_context *c, double *red, double *XY, double *W, double
         double *cpart = gpart + plsk::COOP_MAXG * plsk::COOP_GSTRIDE;
         const dim3 grid((K + plsk::COOP_WG - 1) / plsk::COOP_WG), blk(plsk::COOP_WG);
         Scope s(c, PLS_HIP_FAM_SMALL, ((i64)K * M * 3 + (i64)K * (2 * (a + 2)) + K) * 8);
-#define COOP_CASE(MM_) hipLaunchKernelGGL((plsk::coop_update_kernel<MM_>), grid, blk, (size_t)A * sizeof(double), c->stream, \
-                                          red, XY, W, P, Q, R, v, K, M, A, a, nip, (int)c->opt_power_iters, cnt, qraw, gpart, cpart)
-        if (M <= 2) COOP_CASE(2); else if (M <= 4) COOP_CASE(4); else COOP_CASE(8);
-#undef COOP_CASE
+        with_mm(M, [&](auto mm) {
+            hipLaunchKernelGGL((plsk::coop_update_kernel<decltype(mm)::value>), grid, blk, (size_t)A * sizeof(double), c->stream, red, XY, W, P,
+                               Q, R, v, K, M, A, a, nip, (int)c->opt_power_iters, cnt, qraw, gpart, cpart);
+        });
         LAUNCH_CHECK(c);
         return PLS_HIP_OK;
     }

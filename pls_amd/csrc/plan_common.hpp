@@ -118,6 +118,15 @@ int launch_sym_product(pls_hip_context *c, const double *S, int n, const double 
     return PLS_HIP_OK;
 }
 
+// f(std::integral_constant<int, MM>{}) with MM = M rounded up to 2, 4 or 8: the instantiations of the kernels that are
+// templated on the number of responses (1 <= M <= 8)
+template <typename F>
+auto with_mm(int M, F &&f) {
+    if (M <= 2) return f(std::integral_constant<int, 2>{});
+    if (M <= 4) return f(std::integral_constant<int, 4>{});
+    return f(std::integral_constant<int, 8>{});
+}
+
 // Items (problems, folds) per round of a call that works through n of them with per_item_bytes of workspace each: as many as
 // 4 GB and half of the free device memory hold, at most value_cap (index ranges) and env_cap (> 0: the test knob).  0: not even one.
 constexpr i64 ROUND_BYTES = (i64)4 << 30;

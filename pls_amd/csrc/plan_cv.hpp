@@ -49,63 +49,42 @@ int cv_folds_device(pls_hip_context *h, const T *dX, i64 dldx, const T *dY, i64 
     return PLS_HIP_OK;
 }
 
-// Small single-response data (the reference's examples): every fold is a single-launch fit (tiny_kernels.hpp) on the whole X
-// with its held-out rows masked, one workgroup per fold -- no X^T X at all, which for N < K is the smaller object anyway.
+// Small data (the reference's examples): every fold is a single-launch fit (tiny_kernels.hpp) on the whole X with its held-out
+// rows masked, one workgroup -- for the smallest data (N <= 64, K <= 32) one WAVE -- per fold: no X^T X at all, which for N < K
+// is the smaller object anyway.  kind: the kernel pls_hip_cv_folds chose.
+enum class FoldKernel { micro, tiny, tiny_m };  // micro_fit_kernel; tiny_fit_kernel (one response); tiny_fit_m_kernel (2..8)
 template <typename T>
-int cv_folds_tiny(pls_hip_context *h, const T *dX, i64 dldx, const T *dY, i64 N, int Ki, int Ai, const int64_t *test_idx, int ts,
-                  i64 num_folds, double *dE) {
+int cv_folds_single_launch(pls_hip_context *h, FoldKernel kind, const T *dX, i64 dldx, const T *dY, i64 dldy, i64 N, int Ki, int Mi,
+                           int Ai, const int64_t *test_idx, int ts, i64 num_folds, double *dE) {
     const i64 nobs = num_folds * ts;
     CHK(ensure(h, h->cvidx, (size_t)nobs * 8));
     HIPCHK(h, hipMemcpyAsync(h->cvidx.p, test_idx, (size_t)nobs * 8, hipMemcpyHostToDevice, h->stream));
-    const size_t lds = (size_t)2 * Ki * Ai * 8;
-    if (!plsk::raise_dynamic_lds((const void *)plsk::tiny_fit_kernel<T>, (int)plsk::TINY_LDS_MAX)  /* raised once per device: to the most any fit asks for */)
-        return fail(h, PLS_HIP_ERR_DEVICE, "dynamic LDS limit of the single-launch fit could not be raised");
+    const i64 *idx = (const i64 *)h->cvidx.p;
+    const dim3 grid((unsigned)num_folds);
+    const size_t lds = kind == FoldKernel::micro ? 0 : plsk::single_fit_lds_bytes(Ki, Mi, Ai);  // (one wave: static LDS only)
+    const int pit = (int)h->opt_power_iters;
+    double *const none = nullptr;  // fold mode writes E only
     Scope s(h, PLS_HIP_FAM_SMALL, (i64)num_folds * N * Ki * (i64)sizeof(T));
-    hipLaunchKernelGGL((plsk::tiny_fit_kernel<T>), dim3((unsigned)num_folds), dim3(plsk::UPD_THREADS), lds, h->stream, dX, dldx, dY,
-                       (int)N, Ki, Ai, (double *)nullptr, (double *)nullptr, (double *)nullptr, (double *)nullptr, (T *)nullptr,
-                       (i64)0, (double *)nullptr, (const i64 *)h->cvidx.p, ts, nobs, dE);
-    LAUNCH_CHECK(h);
-    return PLS_HIP_OK;
-}
-
-// ... the same for 2..8 responses (tiny_fit_m_kernel in fold mode)
-template <typename T>
-int cv_folds_tiny_m(pls_hip_context *h, const T *dX, i64 dldx, const T *dY, i64 dldy, i64 N, int Ki, int Mi, int Ai,
-                    const int64_t *test_idx, int ts, i64 num_folds, double *dE) {
-    const i64 nobs = num_folds * ts;
-    CHK(ensure(h, h->cvidx, (size_t)nobs * 8));
-    HIPCHK(h, hipMemcpyAsync(h->cvidx.p, test_idx, (size_t)nobs * 8, hipMemcpyHostToDevice, h->stream));
-    const size_t lds = (size_t)(2 * Ki + Mi) * Ai * 8;
-    Scope s(h, PLS_HIP_FAM_SMALL, (i64)num_folds * N * Ki * (i64)sizeof(T));
-#define TINY_M(MM_)                                                                                                          \
-    do {                                                                                                                     \
-        if (!plsk::raise_dynamic_lds((const void *)plsk::tiny_fit_m_kernel<T, MM_>, (int)plsk::TINY_LDS_MAX))               \
-            return fail(h, PLS_HIP_ERR_DEVICE, "dynamic LDS limit of the single-launch fit could not be raised");            \
-        hipLaunchKernelGGL((plsk::tiny_fit_m_kernel<T, MM_>), dim3((unsigned)num_folds), dim3(plsk::UPD_THREADS), lds, h->stream, dX, \
-                           dldx, dY, dldy, (int)N, Ki, Mi, Ai, (int)h->opt_power_iters, (double *)nullptr, (double *)nullptr,  \
-                           (double *)nullptr, (double *)nullptr, (T *)nullptr, (i64)0, (double *)nullptr,                    \
-                           (const i64 *)h->cvidx.p, ts, nobs, dE);                                                           \
-    } while (0)
-    if (Mi <= 2) TINY_M(2); else if (Mi <= 4) TINY_M(4); else TINY_M(8);
-#undef TINY_M
-    LAUNCH_CHECK(h);
-    return PLS_HIP_OK;
-}
-
-// ... and the smallest data (N <= 64, K <= 32): one WAVE per fold (micro_fit_kernel)
-template <typename T>
-int cv_folds_micro(pls_hip_context *h, const T *dX, i64 dldx, const T *dY, i64 dldy, i64 N, int Ki, int Mi, int Ai,
-                   const int64_t *test_idx, int ts, i64 num_folds, double *dE) {
-    const i64 nobs = num_folds * ts;
-    CHK(ensure(h, h->cvidx, (size_t)nobs * 8));
-    HIPCHK(h, hipMemcpyAsync(h->cvidx.p, test_idx, (size_t)nobs * 8, hipMemcpyHostToDevice, h->stream));
-    Scope s(h, PLS_HIP_FAM_SMALL, (i64)num_folds * N * Ki * (i64)sizeof(T));
-#define MICRO(MM_)                                                                                                           \
-    hipLaunchKernelGGL((plsk::micro_fit_kernel<T, MM_>), dim3((unsigned)num_folds), dim3(plsk::WAVE), 0, h->stream, dX, dldx, dY, \
-                       dldy, (int)N, Ki, Mi, Ai, (int)h->opt_power_iters, (double *)nullptr, (double *)nullptr, (double *)nullptr, \
-                       (double *)nullptr, (T *)nullptr, (i64)0, (double *)nullptr, (const i64 *)h->cvidx.p, ts, nobs, dE)
-    if (Mi <= 2) MICRO(2); else if (Mi <= 4) MICRO(4); else MICRO(8);
-#undef MICRO
+    if (kind == FoldKernel::micro) {
+        with_mm(Mi, [&](auto mm) {
+            hipLaunchKernelGGL((plsk::micro_fit_kernel<T, decltype(mm)::value>), grid, dim3(plsk::WAVE), lds, h->stream, dX, dldx, dY, dldy, (int)N,
+                               Ki, Mi, Ai, pit, none, none, none, none, (T *)nullptr, (i64)0, none, idx, ts, nobs, dE);
+        });
+    } else if (kind == FoldKernel::tiny) {
+        if (!plsk::raise_dynamic_lds((const void *)plsk::tiny_fit_kernel<T>, (int)plsk::TINY_LDS_MAX)  /* raised once per device: to the most any fit asks for */)
+            return fail(h, PLS_HIP_ERR_DEVICE, "dynamic LDS limit of the single-launch fit could not be raised");
+        hipLaunchKernelGGL((plsk::tiny_fit_kernel<T>), grid, dim3(plsk::UPD_THREADS), lds, h->stream, dX, dldx, dY, (int)N, Ki, Ai, none, none,
+                           none, none, (T *)nullptr, (i64)0, none, idx, ts, nobs, dE);
+    } else {
+        CHK(with_mm(Mi, [&](auto mm) {
+            constexpr int MM = decltype(mm)::value;
+            if (!plsk::raise_dynamic_lds((const void *)plsk::tiny_fit_m_kernel<T, MM>, (int)plsk::TINY_LDS_MAX))
+                return fail(h, PLS_HIP_ERR_DEVICE, "dynamic LDS limit of the single-launch fit could not be raised");
+            hipLaunchKernelGGL((plsk::tiny_fit_m_kernel<T, MM>), grid, dim3(plsk::UPD_THREADS), lds, h->stream, dX, dldx, dY, dldy, (int)N, Ki,
+                               Mi, Ai, pit, none, none, none, none, (T *)nullptr, (i64)0, none, idx, ts, nobs, dE);
+            return (int)PLS_HIP_OK;
+        }));
+    }
     LAUNCH_CHECK(h);
     return PLS_HIP_OK;
 }

@@ -39,6 +39,34 @@ inline void resident_done(pls_hip_context *c) {
     t.any[d] = true;
 }
 
+// The workspace of a resident launch in c->resident: 256 bytes of arrival counters (two, 64 bytes apart, zero before their
+// launch), then `payload` bytes; and what its bounded waits report to (resident_kernels.hpp, ResidentSync)
+int resident_workspace(pls_hip_context *c, size_t payload, plsk::ResidentSync &sy) {
+    if (c->resident.bytes < 256 + payload) {
+        CHK(ensure(c, c->resident, 256 + payload));
+        HIPCHK(c, hipMemsetAsync(c->resident.p, 0, 256, c->stream));  // both counters start from zero
+        c->resident_launches = 0;
+    }
+    sy.status = c->diverged_dev + 1;
+    sy.limit = (long long)(0.05 * 1e8);  // 50 ms of the 100 MHz wall clock
+#ifdef PLS_HIP_TESTING
+    if (const char *e = getenv("PLS_HIP_TEST_RESIDENT_LIMIT_TICKS")) sy.limit = atoll(e);  // (the time-out path, tests only)
+#endif
+    return PLS_HIP_OK;
+}
+
+// ... of a fit that exchanges once per component: two parities of G partial rows of LP doubles, this launch's counter and the next one's
+int resident_sync(pls_hip_context *c, int G, int LP, plsk::ResidentSync &sy) {
+    CHK(resident_workspace(c, (size_t)2 * G * LP * 8, sy));
+    unsigned *ctr = (unsigned *)c->resident.p;
+    sy.bar = ctr + 16 * (c->resident_launches & 1);        // (64 bytes apart)
+    sy.bar_next = ctr + 16 * ((c->resident_launches + 1) & 1);
+    ++c->resident_launches;
+    sy.part = (double *)((char *)c->resident.p + 256);
+    sy.LP = LP;
+    return PLS_HIP_OK;
+}
+
 // ---- the fit on device pointers -----------------------------------------------------------
 template <typename T>
 int fit_device(pls_hip_context *c, const T *X, i64 ldx, const T *Y, i64 ldy, i64 N, int K, int M,
@@ -55,15 +83,19 @@ int fit_device(pls_hip_context *c, const T *X, i64 ldx, const T *Y, i64 ldy, i64
     // three launches per component, whose dispatch latency would be the entire cost.  The reference's sequence, so the
     // KERNEL plan and AUTO (also when X^T X came with the upload: one launch beats the K x K loop's sixty);
     // an explicit NIPALS or GRAM request keeps its own kernels.
-    if (method == PLS_HIP_KERNEL_TYPE1 && (c->opt_algo == PLS_HIP_ALGO_KERNEL || c->opt_algo == PLS_HIP_ALGO_AUTO) && c->opt_fuse &&
-        !c->reducer && c->env.tiny && plsk::tiny_fit_covers(N, K, M, A, ldx, sizeof(T)) &&
+    const bool single_launch = method == PLS_HIP_KERNEL_TYPE1 && (c->opt_algo == PLS_HIP_ALGO_KERNEL || c->opt_algo == PLS_HIP_ALGO_AUTO) &&
+                               c->opt_fuse && !c->reducer && c->env.tiny;  // what every single-launch route below asks for
+    // (the per-component resident routes: a replayed graph would re-use one launch's arrival counter)
+    const bool resident_ok = single_launch && c->env.resident && !c->opt_graph && plsk::elem_aligned<T>(X) && plsk::elem_aligned<T>(Y) && Tm;
+    const size_t fit_lds = plsk::single_fit_lds_bytes(K, M, A);  // dynamic LDS of the one-workgroup and the per-component resident kernels
+    const i64 fit_bytes = ((i64)N * K + (i64)N * M + (i64)N * A) * (i64)sizeof(T) + (3 * (i64)K + M) * A * 8;
+    if (single_launch && plsk::tiny_fit_covers(N, K, M, A, ldx, sizeof(T)) &&
         !plsk::micro_fit_covers(N, K, M, A, ldx, sizeof(T))) {  // (the smallest data: one wave is faster than 1024 threads' barriers, below)
-        const size_t lds = (size_t)2 * K * A * 8;
         if (!plsk::raise_dynamic_lds((const void *)plsk::tiny_fit_kernel<T>, (int)plsk::TINY_LDS_MAX)  /* raised once per device: to the most any fit asks for */)
             return fail(c, PLS_HIP_ERR_DEVICE, "dynamic LDS limit of the single-launch fit could not be raised");
         Range r_fit("pls_hip_fit (single launch)");
-        Scope s(c, PLS_HIP_FAM_SMALL, ((i64)N * K + (i64)N * M + (i64)N * A) * (i64)sizeof(T) + (3 * (i64)K + M) * A * 8);
-        hipLaunchKernelGGL((plsk::tiny_fit_kernel<T>), dim3(1), dim3(plsk::UPD_THREADS), lds, c->stream, X, ldx, Y, (int)N, K, A,
+        Scope s(c, PLS_HIP_FAM_SMALL, fit_bytes);
+        hipLaunchKernelGGL((plsk::tiny_fit_kernel<T>), dim3(1), dim3(plsk::UPD_THREADS), fit_lds, c->stream, X, ldx, Y, (int)N, K, A,
                            W, P, Q, R, Tm, ldt, B, (const i64 *)nullptr, 0, (i64)0, (double *)nullptr);
         LAUNCH_CHECK(c);
         return PLS_HIP_OK;
@@ -73,8 +105,7 @@ int fit_device(pls_hip_context *c, const T *X, i64 ldx, const T *Y, i64 ldy, i64
     // fits below exchange once per component.  An explicit KERNEL request keeps the reference's TYPE1 arithmetic (below).
     if (method == PLS_HIP_KERNEL_TYPE1 && (c->opt_algo == PLS_HIP_ALGO_AUTO || c->env.resident_gram == 2) && c->opt_fuse && !c->reducer &&
         c->env.tiny && c->env.resident && c->env.resident_gram && !c->opt_graph && plsk::elem_aligned<T>(X) && plsk::elem_aligned<T>(Y) && Tm &&
-        !plsk::tiny_fit_covers(N, K, M, A, ldx, sizeof(T)) && !plsk::tiny_fit_m_covers(N, K, M, A, ldx, sizeof(T)) &&
-        !plsk::micro_fit_covers(N, K, M, A, ldx, sizeof(T))) {
+        !plsk::single_fit_covers(N, K, M, A, ldx, sizeof(T)) && !plsk::micro_fit_covers(N, K, M, A, ldx, sizeof(T))) {
         int G = plsk::resident_gram_grid(N, K, M, A, ldx, sizeof(T), c->num_cu);
         if (G > 0 && host_flags(c)) {
             plsk::ResidentGram rg;
@@ -97,12 +128,7 @@ int fit_device(pls_hip_context *c, const T *X, i64 ldx, const T *Y, i64 ldy, i64
                 if ((i64)rg.rows_per * kp > rg.big && rg.big < 16384 && 16384 + plsk::RG_SMALL + plsk::resident_gram_extra(K, M, A) <= plsk::RG_LDS_DOUBLES - (M > 1 ? 256 : 0))
                     rg.big = 16384;
             }
-            const size_t need = 256 + ((size_t)(G + 1) * rg.LP + (size_t)K * A) * 8;
-            if (c->resident.bytes < need) {
-                CHK(ensure(c, c->resident, need));
-                HIPCHK(c, hipMemsetAsync(c->resident.p, 0, 256, c->stream));  // both counters start from zero
-                c->resident_launches = 0;
-            }
+            CHK(resident_workspace(c, ((size_t)(G + 1) * rg.LP + (size_t)K * A) * 8, rg.sy));
             const size_t lds = ((size_t)rg.big + plsk::RG_SMALL + (size_t)plsk::resident_gram_extra(K, M, A)) * 8;
             const void *fn = rg.rs > 0 ? (M <= 1 ? (const void *)plsk::resident_gram_fit_kernel<T, 1, true> : (const void *)plsk::resident_gram_fit_kernel<T, 2, true>)
                              : M <= 1 ? (const void *)plsk::resident_gram_fit_kernel<T, 1>
@@ -121,11 +147,6 @@ int fit_device(pls_hip_context *c, const T *X, i64 ldx, const T *Y, i64 ldy, i64
             rg.part = (double *)((char *)c->resident.p + 256);
             rg.gred = rg.part + (size_t)G * rg.LP;
             rg.rshare = rg.gred + rg.LP;
-            rg.sy.status = c->diverged_dev + 1;
-            rg.sy.limit = (long long)(0.05 * 1e8);  // 50 ms of the 100 MHz wall clock
-#ifdef PLS_HIP_TESTING
-            if (const char *e = getenv("PLS_HIP_TEST_RESIDENT_LIMIT_TICKS")) rg.sy.limit = atoll(e);
-#endif
             Range r_fit("pls_hip_fit (single launch, resident, X^T X)");
             Scope s(c, PLS_HIP_FAM_SMALL, (2 * (i64)N * K + (i64)N * M + (i64)N * A) * (i64)sizeof(T) + (3 * (i64)K + M) * A * 8);
             resident_turn(c);
@@ -145,40 +166,21 @@ int fit_device(pls_hip_context *c, const T *X, i64 ldx, const T *Y, i64 ldy, i64
     }
     // Mid-size single-response data (beyond one workgroup's 1024 rows, up to ~50 MB): the same single launch on up to 256
     // workgroups with one grid-wide exchange per component (resident_kernels.hpp)
-    if (method == PLS_HIP_KERNEL_TYPE1 && (c->opt_algo == PLS_HIP_ALGO_KERNEL || c->opt_algo == PLS_HIP_ALGO_AUTO) && c->opt_fuse &&
-        !c->reducer && c->env.tiny && c->env.resident && !c->opt_graph /* (a replayed graph would re-use one launch's arrival counter) */ &&
-        plsk::elem_aligned<T>(X) && plsk::elem_aligned<T>(Y) && Tm) {
+    if (resident_ok && M == 1) {
         // (the score columns go out through one buffer descriptor per workgroup: A ld s below 2^31)
         const int wps = (i64)A * ldt * (i64)sizeof(T) < (1ll << 31) ? plsk::resident_wps(N, K, M, A, ldx, sizeof(T), c->num_cu) : 0;
         if (wps > 0 && host_flags(c)) {
             const int G = (int)((N + (i64)plsk::WAVE * wps - 1) / ((i64)plsk::WAVE * wps));
-            const int LP = (K + 1 + 7) & ~7;
-            const size_t need = 256 + (size_t)2 * G * LP * 8;
-            if (c->resident.bytes < need) {
-                CHK(ensure(c, c->resident, need));
-                HIPCHK(c, hipMemsetAsync(c->resident.p, 0, 256, c->stream));  // both counters start from zero
-                c->resident_launches = 0;
-            }
             if (!plsk::raise_dynamic_lds((const void *)plsk::resident_fit_kernel<T>, (int)plsk::TINY_LDS_MAX))
                 return fail(c, PLS_HIP_ERR_DEVICE, "dynamic LDS limit of the resident fit could not be raised");
             plsk::ResidentSync sy;
-            unsigned *ctr = (unsigned *)c->resident.p;
-            sy.bar = ctr + 16 * (c->resident_launches & 1);        // (64 bytes apart)
-            sy.bar_next = ctr + 16 * ((c->resident_launches + 1) & 1);
-            ++c->resident_launches;
-            sy.part = (double *)((char *)c->resident.p + 256);
-            sy.status = c->diverged_dev + 1;
-            sy.limit = (long long)(0.05 * 1e8);  // 50 ms of the 100 MHz wall clock
-#ifdef PLS_HIP_TESTING
-            if (const char *e = getenv("PLS_HIP_TEST_RESIDENT_LIMIT_TICKS")) sy.limit = atoll(e);  // (the time-out path, tests only)
-#endif
-            sy.LP = LP;
+            CHK(resident_sync(c, G, (K + 1 + 7) & ~7, sy));
             Range r_fit("pls_hip_fit (single launch, resident)");
-            Scope s(c, PLS_HIP_FAM_SMALL, ((i64)N * K + (i64)N + (i64)N * A) * (i64)sizeof(T) + (3 * (i64)K + 1) * A * 8);
+            Scope s(c, PLS_HIP_FAM_SMALL, fit_bytes);
             // all G workgroups must be resident together: the resident fits of ONE process take turns (an event chain per
             // device across its streams); a foreign kernel holding CUs ends in the bounded wait's error, not in a hang
             resident_turn(c);
-            hipLaunchKernelGGL((plsk::resident_fit_kernel<T>), dim3(G), dim3(plsk::UPD_THREADS), (size_t)2 * K * A * 8, c->stream, X, ldx, Y,
+            hipLaunchKernelGGL((plsk::resident_fit_kernel<T>), dim3(G), dim3(plsk::UPD_THREADS), fit_lds, c->stream, X, ldx, Y,
                                N, K, A, W, P, Q, R, Tm, ldt, B, wps, sy);
             LAUNCH_CHECK(c);
             resident_done(c);
@@ -186,78 +188,52 @@ int fit_device(pls_hip_context *c, const T *X, i64 ldx, const T *Y, i64 ldy, i64
         }
     }
     // ... and the same for 2..8 responses (resident_fit_m_kernel)
-    if (method == PLS_HIP_KERNEL_TYPE1 && (c->opt_algo == PLS_HIP_ALGO_KERNEL || c->opt_algo == PLS_HIP_ALGO_AUTO) && c->opt_fuse &&
-        !c->reducer && c->env.tiny && c->env.resident && !c->opt_graph /* (a replayed graph would re-use one launch's arrival counter) */ &&
-        plsk::elem_aligned<T>(X) && plsk::elem_aligned<T>(Y) && Tm) {
-        const int wps = plsk::resident_m_wps(N, K, M, A, ldx, sizeof(T), c->num_cu);
+    if (resident_ok && M >= 2) {
+        const int wps = plsk::resident_wps(N, K, M, A, ldx, sizeof(T), c->num_cu);
         if (wps > 0 && host_flags(c)) {
             const int G = (int)((N + (i64)plsk::WAVE * wps - 1) / ((i64)plsk::WAVE * wps));
-            const int LP = (std::max(K + 1, std::min(K * M, (int)plsk::UPD_THREADS)) + 7) & ~7;
-            const size_t need = 256 + (size_t)2 * G * LP * 8;
-            if (c->resident.bytes < need) {
-                CHK(ensure(c, c->resident, need));
-                HIPCHK(c, hipMemsetAsync(c->resident.p, 0, 256, c->stream));
-                c->resident_launches = 0;
-            }
-            plsk::ResidentSync sy;
-            unsigned *ctr = (unsigned *)c->resident.p;
-            sy.bar = ctr + 16 * (c->resident_launches & 1);
-            sy.bar_next = ctr + 16 * ((c->resident_launches + 1) & 1);
-            ++c->resident_launches;
-            sy.part = (double *)((char *)c->resident.p + 256);
-            sy.status = c->diverged_dev + 1;
-            sy.limit = (long long)(0.05 * 1e8);
-#ifdef PLS_HIP_TESTING
-            if (const char *e = getenv("PLS_HIP_TEST_RESIDENT_LIMIT_TICKS")) sy.limit = atoll(e);
-#endif
-            sy.LP = LP;
-            const size_t lds = (size_t)(2 * K + M) * A * 8;
             Range r_fit("pls_hip_fit (single launch, resident)");
-            Scope s(c, PLS_HIP_FAM_SMALL, ((i64)N * K + (i64)N * M + (i64)N * A) * (i64)sizeof(T) + (3 * (i64)K + M) * A * 8);
-#define RES_M(MM_)                                                                                                              \
-    do {                                                                                                                        \
-        if (!plsk::raise_dynamic_lds((const void *)plsk::resident_fit_m_kernel<T, MM_>, (int)plsk::TINY_LDS_MAX))                 \
-            return fail(c, PLS_HIP_ERR_DEVICE, "dynamic LDS limit of the resident fit could not be raised");                      \
-        resident_turn(c);                                                                                                       \
-        hipLaunchKernelGGL((plsk::resident_fit_m_kernel<T, MM_>), dim3(G), dim3(plsk::UPD_THREADS), lds, c->stream, X, ldx, Y, ldy,  \
-                           N, K, M, A, (int)c->opt_power_iters, W, P, Q, R, Tm, ldt, B, wps, sy);                               \
-    } while (0)
-            if (M <= 2) RES_M(2); else if (M <= 4) RES_M(4); else RES_M(8);
-#undef RES_M
+            Scope s(c, PLS_HIP_FAM_SMALL, fit_bytes);
+            CHK(with_mm(M, [&](auto mm) {
+                constexpr int MM = decltype(mm)::value;
+                // (as in the one-response route: a refusal here leaves the launch counter where it was)
+                if (!plsk::raise_dynamic_lds((const void *)plsk::resident_fit_m_kernel<T, MM>, (int)plsk::TINY_LDS_MAX))
+                    return fail(c, PLS_HIP_ERR_DEVICE, "dynamic LDS limit of the resident fit could not be raised");
+                plsk::ResidentSync sy;
+                CHK(resident_sync(c, G, (std::max(K + 1, std::min(K * M, (int)plsk::UPD_THREADS)) + 7) & ~7, sy));
+                resident_turn(c);
+                hipLaunchKernelGGL((plsk::resident_fit_m_kernel<T, MM>), dim3(G), dim3(plsk::UPD_THREADS), fit_lds, c->stream, X, ldx, Y, ldy,
+                                   N, K, M, A, (int)c->opt_power_iters, W, P, Q, R, Tm, ldt, B, wps, sy);
+                return (int)PLS_HIP_OK;
+            }));
             LAUNCH_CHECK(c);
             resident_done(c);
             return PLS_HIP_OK;
         }
     }
     // The smallest problems (N <= 64, K <= 32, 1..8 responses: the reference's README example) as ONE WAVE (micro_fit_kernel)
-    if (method == PLS_HIP_KERNEL_TYPE1 && (c->opt_algo == PLS_HIP_ALGO_KERNEL || c->opt_algo == PLS_HIP_ALGO_AUTO) && c->opt_fuse &&
-        !c->reducer && c->env.tiny && plsk::micro_fit_covers(N, K, M, A, ldx, sizeof(T))) {
+    if (single_launch && plsk::micro_fit_covers(N, K, M, A, ldx, sizeof(T))) {
         Range r_fit("pls_hip_fit (single launch, one wave)");
-        Scope s(c, PLS_HIP_FAM_SMALL, ((i64)N * K + (i64)N * M + (i64)N * A) * (i64)sizeof(T) + (3 * (i64)K + M) * A * 8);
-#define MICRO(MM_)                                                                                                           \
-    hipLaunchKernelGGL((plsk::micro_fit_kernel<T, MM_>), dim3(1), dim3(plsk::WAVE), 0, c->stream, X, ldx, Y, ldy, (int)N, K, M, A, \
-                       (int)c->opt_power_iters, W, P, Q, R, Tm, ldt, B, (const i64 *)nullptr, 0, (i64)0, (double *)nullptr)
-        if (M <= 2) MICRO(2); else if (M <= 4) MICRO(4); else MICRO(8);
-#undef MICRO
+        Scope s(c, PLS_HIP_FAM_SMALL, fit_bytes);
+        with_mm(M, [&](auto mm) {
+            hipLaunchKernelGGL((plsk::micro_fit_kernel<T, decltype(mm)::value>), dim3(1), dim3(plsk::WAVE), 0, c->stream, X, ldx, Y, ldy, (int)N,
+                               K, M, A, (int)c->opt_power_iters, W, P, Q, R, Tm, ldt, B, (const i64 *)nullptr, 0, (i64)0, (double *)nullptr);
+        });
         LAUNCH_CHECK(c);
         return PLS_HIP_OK;
     }
     // ... and the same for 2..8 responses (tiny_fit_m_kernel: the reference's own example, README.md:23, is such a fit)
-    if (method == PLS_HIP_KERNEL_TYPE1 && (c->opt_algo == PLS_HIP_ALGO_KERNEL || c->opt_algo == PLS_HIP_ALGO_AUTO) && c->opt_fuse &&
-        !c->reducer && c->env.tiny && plsk::tiny_fit_m_covers(N, K, M, A, ldx, sizeof(T))) {
-        const size_t lds = (size_t)(2 * K + M) * A * 8;
+    if (single_launch && plsk::tiny_fit_m_covers(N, K, M, A, ldx, sizeof(T))) {
         Range r_fit("pls_hip_fit (single launch)");
-        Scope s(c, PLS_HIP_FAM_SMALL, ((i64)N * K + (i64)N * M + (i64)N * A) * (i64)sizeof(T) + (3 * (i64)K + M) * A * 8);
-#define TINY_M(MM_)                                                                                                          \
-    do {                                                                                                                     \
-        if (!plsk::raise_dynamic_lds((const void *)plsk::tiny_fit_m_kernel<T, MM_>, (int)plsk::TINY_LDS_MAX))               \
-            return fail(c, PLS_HIP_ERR_DEVICE, "dynamic LDS limit of the single-launch fit could not be raised");            \
-        hipLaunchKernelGGL((plsk::tiny_fit_m_kernel<T, MM_>), dim3(1), dim3(plsk::UPD_THREADS), lds, c->stream, X, ldx, Y, ldy,  \
-                           (int)N, K, M, A, (int)c->opt_power_iters, W, P, Q, R, Tm, ldt, B, (const i64 *)nullptr, 0, (i64)0,  \
-                           (double *)nullptr);                                                                               \
-    } while (0)
-        if (M <= 2) TINY_M(2); else if (M <= 4) TINY_M(4); else TINY_M(8);
-#undef TINY_M
+        Scope s(c, PLS_HIP_FAM_SMALL, fit_bytes);
+        CHK(with_mm(M, [&](auto mm) {
+            constexpr int MM = decltype(mm)::value;
+            if (!plsk::raise_dynamic_lds((const void *)plsk::tiny_fit_m_kernel<T, MM>, (int)plsk::TINY_LDS_MAX))
+                return fail(c, PLS_HIP_ERR_DEVICE, "dynamic LDS limit of the single-launch fit could not be raised");
+            hipLaunchKernelGGL((plsk::tiny_fit_m_kernel<T, MM>), dim3(1), dim3(plsk::UPD_THREADS), fit_lds, c->stream, X, ldx, Y, ldy, (int)N, K, M,
+                               A, (int)c->opt_power_iters, W, P, Q, R, Tm, ldt, B, (const i64 *)nullptr, 0, (i64)0, (double *)nullptr);
+            return (int)PLS_HIP_OK;
+        }));
         LAUNCH_CHECK(c);
         return PLS_HIP_OK;
     }

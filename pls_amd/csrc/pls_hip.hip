@@ -45,8 +45,8 @@ using plsk::i64;
 
 #include "ctx.hpp"
 #include "launch_products.hpp"
-#include "launch_update.hpp"
 #include "plan_common.hpp"
+#include "launch_update.hpp"
 #include "plan_dual.hpp"
 #include "plan_fit.hpp"
 #include "host_entry.hpp"
@@ -596,25 +596,14 @@ int pls_hip_cv_folds(pls_hip_handle h, const void *X, int64_t ldx, const void *Y
     }
     if (rc != PLS_HIP_ERR_ALLOC) {
         // (the sample-space route took the call)
-    } else if (micro) {
+    } else if (micro || tiny || tiny_m) {  // a single-launch fit per fold, in this order of preference
+        const FoldKernel kind = micro ? FoldKernel::micro : tiny ? FoldKernel::tiny : FoldKernel::tiny_m;
         if (dtype == PLS_HIP_F64)
-            rc = cv_folds_micro<double>(h, (const double *)dX, dldx, (const double *)dY, dldy, N, (int)K, (int)M, (int)A, test_idx,
-                                        (int)test_size, num_folds, dE);
+            rc = cv_folds_single_launch<double>(h, kind, (const double *)dX, dldx, (const double *)dY, dldy, N, (int)K, (int)M, (int)A,
+                                                test_idx, (int)test_size, num_folds, dE);
         else
-            rc = cv_folds_micro<float>(h, (const float *)dX, dldx, (const float *)dY, dldy, N, (int)K, (int)M, (int)A, test_idx,
-                                       (int)test_size, num_folds, dE);
-    } else if (tiny) {
-        if (dtype == PLS_HIP_F64)
-            rc = cv_folds_tiny<double>(h, (const double *)dX, dldx, (const double *)dY, N, (int)K, (int)A, test_idx, (int)test_size, num_folds, dE);
-        else
-            rc = cv_folds_tiny<float>(h, (const float *)dX, dldx, (const float *)dY, N, (int)K, (int)A, test_idx, (int)test_size, num_folds, dE);
-    } else if (tiny_m) {
-        if (dtype == PLS_HIP_F64)
-            rc = cv_folds_tiny_m<double>(h, (const double *)dX, dldx, (const double *)dY, dldy, N, (int)K, (int)M, (int)A, test_idx,
-                                         (int)test_size, num_folds, dE);
-        else
-            rc = cv_folds_tiny_m<float>(h, (const float *)dX, dldx, (const float *)dY, dldy, N, (int)K, (int)M, (int)A, test_idx,
-                                        (int)test_size, num_folds, dE);
+            rc = cv_folds_single_launch<float>(h, kind, (const float *)dX, dldx, (const float *)dY, dldy, N, (int)K, (int)M, (int)A,
+                                               test_idx, (int)test_size, num_folds, dE);
     } else if (cv_batched_covers(h, K, M, A)) {
         if (dtype == PLS_HIP_F64)
             rc = cv_folds_device<double>(h, (const double *)dX, dldx, (const double *)dY, dldy, N, (int)K, (int)M, (int)A,

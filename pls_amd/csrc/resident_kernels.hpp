@@ -32,11 +32,11 @@ struct ResidentSync {
 
 constexpr int RESIDENT_MAX_WG = 256;
 
-// rows per workgroup = 64 * wps; 0: the shape is not covered
+// rows per workgroup = 64 * wps; 0: the shape is not covered.  1 <= M <= 8: resident_fit_kernel (M = 1) or resident_fit_m_kernel
 inline int resident_wps(i64 N, int K, int M, int A, i64 ldx, size_t es, int num_cu) {
-    if (M != 1 || N < 1 || A > K || K < 1 || (i64)TINY_KMAX * ldx * (i64)es >= (1ll << 31)) return 0;
-    if (tiny_fit_covers(N, K, M, A, ldx, es) || micro_fit_covers(N, K, M, A, ldx, es)) return 0;  // (one workgroup / one wave does it)
-    if ((size_t)2 * K * A * 8 > TINY_LDS_MAX) return 0;
+    if (M < 1 || M > 8 || N < 1 || A > K || K < 1 || (i64)TINY_KMAX * ldx * (i64)es >= (1ll << 31)) return 0;
+    if (single_fit_covers(N, K, M, A, ldx, es) || micro_fit_covers(N, K, M, A, ldx, es)) return 0;  // (one workgroup / one wave does it)
+    if (single_fit_lds_bytes(K, M, A) > TINY_LDS_MAX) return 0;
     // the TALLEST row block whose column slices still hold K columns: the fewest workgroups -- a workgroup's work per component
     // is its 26 register values per thread whatever the block's shape, while the exchange costs by the number of partial vectors
     for (int wps = UPD_WAVES; wps >= 1; wps /= 2) {
@@ -260,17 +260,6 @@ __global__ __launch_bounds__(UPD_THREADS) void resident_fit_kernel(const T *__re
 // eigen solver) x G, with X^T Y exchanged once -- the K M values in pieces of at most 1024 -- and [X^T t, t^T t] per component.
 // Dynamic LDS: (2 K + M) A doubles.
 // ---------------------------------------------------------------------------------------------------------------------
-inline int resident_m_wps(i64 N, int K, int M, int A, i64 ldx, size_t es, int num_cu) {
-    if (M < 2 || M > 8 || N < 1 || A > K || K < 1 || (i64)TINY_KMAX * ldx * (i64)es >= (1ll << 31)) return 0;
-    if (tiny_fit_m_covers(N, K, M, A, ldx, es) || micro_fit_covers(N, K, M, A, ldx, es)) return 0;
-    if ((size_t)(2 * K + M) * A * 8 > TINY_LDS_MAX) return 0;
-    for (int wps = UPD_WAVES; wps >= 1; wps /= 2) {
-        const i64 G = (N + (i64)WAVE * wps - 1) / ((i64)WAVE * wps);
-        if (K <= (UPD_WAVES / wps) * TINY_RC && G <= std::min(num_cu, RESIDENT_MAX_WG)) return wps;
-    }
-    return 0;
-}
-
 template <typename T, int MM>
 __global__ __launch_bounds__(UPD_THREADS) void resident_fit_m_kernel(const T *__restrict__ X, i64 ldx, const T *__restrict__ Y, i64 ldy,
                                                                      i64 N, int K, int M, int A, int power_iters,

@@ -12,6 +12,11 @@
 //   t_i   = sum over the S slices of the per-thread partial sum_j x[j] r[s + j*S]           (LDS, fixed order)
 //   p_raw = column sums of x[j] * t_i over the rows: wave_multi_sum inside the wave, then the wps waves of a slice in order
 // Every sum has a fixed order: equal inputs give equal bits.
+// The loop bodies of tiny_fit_kernel, tiny_fit_m_kernel and of the two resident kernels (resident_kernels.hpp) repeat each other
+// statement for statement ON PURPOSE.  Built from shared __forceinline__ steps all four kept their compiler reports (at the 128
+// registers of a 1024-thread workgroup) and their bits, but on an MI355X resident_fit_m_kernel ran 5-7 % slower at two responses,
+// tiny_fit_m_kernel 0.5-1.6 % and resident_fit_kernel in fp32 about 1 % slower (profiles/single_fit): an arithmetic change is
+// made in all four.
 #pragma once
 #include "fused_kernels.hpp"  // raw buffer descriptors
 #include "small_kernels.hpp"
@@ -70,12 +75,17 @@ __device__ __forceinline__ void st_score(__amdgpu_buffer_rsrc_t r, uint32_t voff
     }
 }
 
-constexpr size_t TINY_LDS_MAX = 96 * 1024;  // dynamic LDS: the P and R columns, 2 * K * A doubles
-inline bool tiny_fit_covers(i64 N, int K, int M, int A, i64 ldx, size_t es) {
-    if (M != 1 || N < 1 || N > UPD_THREADS || A > K || (i64)TINY_KMAX * ldx * (i64)es >= (1 << 30)) return false;  // 32-bit byte offsets
+constexpr size_t TINY_LDS_MAX = 96 * 1024;
+// dynamic LDS of a single-launch fit: the P and R columns as they are produced, with several responses the Q columns as well
+inline size_t single_fit_lds_bytes(int K, int M, int A) { return M == 1 ? (size_t)2 * K * A * 8 : (size_t)(2 * K + M) * A * 8; }
+// one workgroup takes the fit: tiny_fit_kernel (M = 1) or tiny_fit_m_kernel (2 <= M <= 8)
+inline bool single_fit_covers(i64 N, int K, int M, int A, i64 ldx, size_t es) {
+    if (M < 1 || M > 8 || N < 1 || N > UPD_THREADS || A > K || (i64)TINY_KMAX * ldx * (i64)es >= (1 << 30)) return false;  // 32-bit byte offsets
     const TinyShape sh((int)N);
-    return sh.S >= 1 && K <= sh.S * TINY_RC && (size_t)2 * K * A * 8 <= TINY_LDS_MAX;
+    return sh.S >= 1 && K <= sh.S * TINY_RC && single_fit_lds_bytes(K, M, A) <= TINY_LDS_MAX;
 }
+inline bool tiny_fit_covers(i64 N, int K, int M, int A, i64 ldx, size_t es) { return M == 1 && single_fit_covers(N, K, M, A, ldx, es); }
+inline bool tiny_fit_m_covers(i64 N, int K, int M, int A, i64 ldx, size_t es) { return M >= 2 && single_fit_covers(N, K, M, A, ldx, es); }
 
 // block_sum (common.hpp) on lds_barrier
 __device__ __forceinline__ double tiny_block_sum(double v, double *smem) {
@@ -275,12 +285,6 @@ __global__ __launch_bounds__(UPD_THREADS) void tiny_fit_kernel(const T *__restri
 // Fold mode as above, residuals per response: E[m*(nobs*A) + (f*ts + j) + a*nobs].
 // Dynamic LDS: (2 K + M) A doubles (P, R, Q as they are produced).
 // ---------------------------------------------------------------------------------------------------------------------
-inline bool tiny_fit_m_covers(i64 N, int K, int M, int A, i64 ldx, size_t es) {
-    if (M < 2 || M > 8 || N < 1 || N > UPD_THREADS || A > K || (i64)TINY_KMAX * ldx * (i64)es >= (1 << 30)) return false;
-    const TinyShape sh((int)N);
-    return sh.S >= 1 && K <= sh.S * TINY_RC && (size_t)(2 * K + M) * A * 8 <= TINY_LDS_MAX;
-}
-
 template <typename T, int MM>
 __global__ __launch_bounds__(UPD_THREADS) void tiny_fit_m_kernel(const T *__restrict__ X, i64 ldx, const T *__restrict__ Y, i64 ldy,
                                                                  int N, int K, int M, int A, int power_iters,
