@@ -9,12 +9,10 @@
 #include <map>
 #include <utility>
 
+#include "xb_route.hpp"  // i64, WAVE, WG
+
 namespace plsk {
 
-typedef int64_t i64;
-
-constexpr int WAVE = 64;
-constexpr int WG = 256;
 // slices of every reduced vector (reduce_partials_kernel, slice_tail): enough workgroups take part in a reduction, and the
 // consumers add the slices of a value in index order
 constexpr int RED_SLICES = 8;

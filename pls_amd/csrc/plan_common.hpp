@@ -118,14 +118,20 @@ int launch_sym_product(pls_hip_context *c, const double *S, int n, const double 
     return PLS_HIP_OK;
 }
 
-// f(std::integral_constant<int, MM>{}) with MM = M rounded up to 2, 4 or 8: the instantiations of the kernels that are
-// templated on the number of responses (1 <= M <= 8)
-template <typename F>
-auto with_mm(int M, F &&f) {
-    if (M <= 2) return f(std::integral_constant<int, 2>{});
-    if (M <= 4) return f(std::integral_constant<int, 4>{});
-    return f(std::integral_constant<int, 8>{});
+// f(std::integral_constant<int, C>{}) with C the first of the candidates C0, Cs... that is >= v, the last one where none is: the
+// run-time choice among the instantiations of a kernel that is templated on a small integer
+template <int C0, int... Cs, typename F>
+auto pick_int(int v, F &&f) -> decltype(f(std::integral_constant<int, C0>{})) {
+    if constexpr (sizeof...(Cs) == 0) {
+        return f(std::integral_constant<int, C0>{});
+    } else {
+        if (v <= C0) return f(std::integral_constant<int, C0>{});
+        return pick_int<Cs...>(v, f);
+    }
 }
+// MM = M rounded up to 2, 4 or 8: the kernels that are templated on the number of responses (1 <= M <= 8)
+template <typename F>
+auto with_mm(int M, F &&f) { return pick_int<2, 4, 8>(M, f); }
 
 // Items (problems, folds) per round of a call that works through n of them with per_item_bytes of workspace each: as many as
 // 4 GB and half of the free device memory hold, at most value_cap (index ranges) and env_cap (> 0: the test knob).  0: not even one.

@@ -50,12 +50,29 @@ int dual_gram(pls_hip_context *c, const T *X, i64 ldx, int N, int K) {
 // Z (N x cols) = G Ya, dual_gy_kernel with the fewest accumulators that hold cols <= 32 columns
 int launch_dual_gy(pls_hip_context *c, const double *G, const double *Ya, int N, int cols, double *Z) {
     Scope s(c, PLS_HIP_FAM_SMALL, ((i64)N * N + 2 * (i64)N * cols) * 8);
-#define DUAL_GY(MT_) hipLaunchKernelGGL((plsk::dual_gy_kernel<MT_>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, c->stream, G, Ya, N, cols, Z)
-    if (cols <= 1) DUAL_GY(1); else if (cols <= 2) DUAL_GY(2); else if (cols <= 4) DUAL_GY(4); else if (cols <= 8) DUAL_GY(8);
-    else if (cols <= 16) DUAL_GY(16); else DUAL_GY(32);
-#undef DUAL_GY
+    pick_int<1, 2, 4, 8, 16, 32>(cols, [&](auto mt) {
+        hipLaunchKernelGGL((plsk::dual_gy_kernel<decltype(mt)::value>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, c->stream, G, Ya, N, cols, Z);
+    });
     LAUNCH_CHECK(c);
     return PLS_HIP_OK;
+}
+
+// One sweep of dual_xtv_kernel over X, a bracket of PLS_HIP_FAM_XTY: columns c0 .. c0 + nc - 1 (nc <= 64) of X^T V go to W[:, c0 + c]
+// while c0 + c < A and to P[:, c0 + c - A] beyond (dual_kernels.hpp), with the fewest 16-column tiles that hold nc.
+template <typename T>
+int launch_dual_xtv(pls_hip_context *c, const T *X, i64 ldx, int N, i64 K, const double *V, int c0, int nc, int A, double *W, double *P) {
+    Scope s(c, PLS_HIP_FAM_XTY, (i64)N * K * (i64)sizeof(T) + ((i64)N + K) * nc * 8);
+    return pick_int<1, 2, 3, 4>((nc + 15) / 16, [&](auto nct) -> int {
+        const auto kernel = plsk::dual_xtv_kernel<T, decltype(nct)::value>;
+        if (!plsk::raise_dynamic_lds((const void *)kernel, (int)plsk::XTV_LDS_BYTES)) {
+            s.on = false;
+            return fail(c, PLS_HIP_ERR_DEVICE, "dynamic LDS limit of the back-projection could not be raised");
+        }
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((K + plsk::XTV_KB - 1) / plsk::XTV_KB)), dim3(256), plsk::XTV_LDS_BYTES, c->stream, X, ldx, N, K,
+                           V, c0, nc, A, W, P);
+        LAUNCH_CHECK(c);
+        return PLS_HIP_OK;
+    });
 }
 
 template <typename T>
@@ -97,19 +114,7 @@ int fit_dual(pls_hip_context *c, const T *X, i64 ldx, const T *Y, i64 ldy, i64 N
         Range r_b("X^T [U T]");
         for (int c0 = 0; c0 < 2 * A; c0 += plsk::XTV_NC) {
             const int nc = std::min(plsk::XTV_NC, 2 * A - c0);
-            Scope s(c, PLS_HIP_FAM_XTY, (i64)N * K * es + ((i64)N + K) * nc * 8);
-#define DUAL_XTV(NCT_)                                                                                                          \
-    do {                                                                                                                       \
-        if (!plsk::raise_dynamic_lds((const void *)plsk::dual_xtv_kernel<T, NCT_>, (int)plsk::XTV_LDS_BYTES)) {                \
-            s.on = false;                                                                                                      \
-            return fail(c, PLS_HIP_ERR_DEVICE, "dynamic LDS limit of the back-projection could not be raised");                \
-        }                                                                                                                      \
-        hipLaunchKernelGGL((plsk::dual_xtv_kernel<T, NCT_>), dim3((unsigned)(((i64)K + plsk::XTV_KB - 1) / plsk::XTV_KB)),     \
-                           dim3(256), plsk::XTV_LDS_BYTES, c->stream, X, ldx, N, (i64)K, (const double *)V, c0, nc, A, W, P);  \
-    } while (0)
-            if (nc <= 16) DUAL_XTV(1); else if (nc <= 32) DUAL_XTV(2); else if (nc <= 48) DUAL_XTV(3); else DUAL_XTV(4);
-#undef DUAL_XTV
-            LAUNCH_CHECK(c);
+            CHK(launch_dual_xtv<T>(c, X, ldx, N, (i64)K, (const double *)V, c0, nc, A, W, P));
         }
     }
     {

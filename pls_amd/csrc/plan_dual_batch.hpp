@@ -45,19 +45,7 @@ int batch_dual_xtv(pls_hip_context *c, const T *X, i64 ldx, int N, i64 K, const 
     }
     for (int c0 = 0; c0 < cols; c0 += plsk::XTV_NC) {
         const int nc = std::min(plsk::XTV_NC, cols - c0);
-        Scope s(c, PLS_HIP_FAM_XTY, (i64)N * K * es + ((i64)N + K) * nc * 8);
-#define DUAL_XTV(NCT_)                                                                                                          \
-    do {                                                                                                                       \
-        if (!plsk::raise_dynamic_lds((const void *)plsk::dual_xtv_kernel<T, NCT_>, (int)plsk::XTV_LDS_BYTES)) {                \
-            s.on = false;                                                                                                      \
-            return fail(c, PLS_HIP_ERR_DEVICE, "dynamic LDS limit of the back-projection could not be raised");                \
-        }                                                                                                                      \
-        hipLaunchKernelGGL((plsk::dual_xtv_kernel<T, NCT_>), dim3((unsigned)((K + plsk::XTV_KB - 1) / plsk::XTV_KB)), dim3(256), \
-                           plsk::XTV_LDS_BYTES, c->stream, X, ldx, N, K, V, c0, nc, cols, out, (double *)nullptr);             \
-    } while (0)
-        if (nc <= 16) DUAL_XTV(1); else if (nc <= 32) DUAL_XTV(2); else if (nc <= 48) DUAL_XTV(3); else DUAL_XTV(4);
-#undef DUAL_XTV
-        LAUNCH_CHECK(c);
+        CHK(launch_dual_xtv<T>(c, X, ldx, N, K, V, c0, nc, cols, out, (double *)nullptr));  // (A = cols: everything to `out`)
     }
     return PLS_HIP_OK;
 }

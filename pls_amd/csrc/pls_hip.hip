@@ -44,6 +44,7 @@
 using plsk::i64;
 
 #include "ctx.hpp"
+#include "xb_route.hpp"
 #include "launch_products.hpp"
 #include "plan_common.hpp"
 #include "launch_update.hpp"

@@ -30,12 +30,7 @@
 
 namespace plsk {
 
-constexpr int XB4_WG = 1024;
-// column steps per batch: 4 (2 where the accumulators of fp32 storage's 4-row packs leave no room) -- 8 fit the registers up to
-// 20 fp64 columns and are 4 % slower with the barrier (0.757 against 0.730 ms; 2: 0.723, 1: 0.791)
-__host__ __device__ constexpr int xb4_u(int v, int ncg) { return v * ncg > 20 ? 2 : 4; }
-__host__ __device__ constexpr int xb4_kp(int K, int u) { return (K + (4 * u > 32 ? 4 * u : 32) - 1) / (4 * u > 32 ? 4 * u : 32) * (4 * u > 32 ? 4 * u : 32); }  // rows of Bm in LDS
-__host__ __device__ constexpr int xb4_stride(int ncg) { return (8 * ncg) % 64 == 0 ? 4 * ncg + 4 : 4 * ncg; }  // (k-rows on disjoint banks)
+// XB4_WG, xb4_u, xb4_kp, xb4_stride: xb_route.hpp (the launch geometry needs them too)
 
 // MAP, WGT, UU, AUXL, STAUX, BAR: the choices the header's measurements settled (tune/xb4_tune.hip instantiates the others)
 template <typename T, int V, int NCG, int MAP = 0, int WGT = XB4_WG, int UU = 0, int AUXL = 2, int STAUX = 2, int BAR = 1>

@@ -21,10 +21,7 @@ namespace plsk {
 
 __host__ __device__ constexpr int xb4w_u(int v, int ncg) { return v * ncg > 10 ? 2 : 4; }  // column steps per batch
 
-// rows of Bm per window (a power of two: the staging's index arithmetic is shifts): as many as two buffers of [KC][ST] doubles
-// fit in ~150 KB of LDS and 8 doubles per thread carry -- 1,024 for 8 columns, 512 up to 16, 256 beyond
-// (fp32 storage, V = 4 rows per lane: twice the accumulators -- 128 rows from 16 columns on, so that nothing spills in the loop)
-__host__ __device__ constexpr int xb4w_kcl2(int v, int ncg) { return ncg <= 2 ? 10 : ncg <= 3 ? 9 : v > 2 ? 7 : ncg <= 4 ? 9 : 8; }
+// xb4w_kcl2, rows of Bm per window (log2): xb_route.hpp
 
 template <typename T, int V, int NCG>
 __global__ __launch_bounds__(XB4_WG) void xb_mfma4w_kernel(const T *__restrict__ X, i64 ldx, i64 N, int K, const double *__restrict__ Bm,

@@ -210,35 +210,40 @@ def _code(tdt):
 # X * Bm (pls_hip_xb): every kernel family of launch_xb
 # ------------------------------------------------------------------------------------------------------------------------
 
-XB_CASES = [
-    # N, K, C, dt, X layout, out layout, PLS_HIP_XB4, the route
-    (600001, 16, 1, "f64", "aligned", "aligned", None),     # xb_kernel<2, 1>: wide (>= 4 row groups per CU of 512 rows)
-    (600001, 16, 2, "f64", "aligned", "aligned", None),     # xb_kernel<2, 2>
-    (600001, 16, 3, "f64", "aligned", "aligned", None),     # xb_kernel<2, 4> with 3 columns
-    (600001, 16, 3, "f64", "eigen", "eigen", None),         # xb_kernel<1, 4>: narrow
-    (1001, 37, 2, "f64", "eigen", "eigen", None),           # xb_kernel<1, 2>, a short matrix
-    (1048579, 8, 3, "f32", "aligned", "aligned", None),     # xb_kernel<4, 4> fp32
-    (4099, 30, 1, "f32", "eigen", "eigen", None),           # xb_kernel<1, 1> fp32
-    (512, 20000, 1, "f64", "aligned", "aligned", None),     # xb_split_kernel<1, 1> (too few row groups for v2) + finish
-    (5000, 1200, 3, "f64", "aligned", "aligned", None),     # xb_split_kernel<2, 4> + finish
-    (300, 9000, 6, "f64", "eigen", "eigen", None),          # xb_split_kernel<1, 4> then <1, 2> (below 32 MB: not the MFMA split)
-    (2100, 3000, 2, "f32", "eigen", "aligned", None),       # xb_split_kernel<1, 2> fp32
-    (600001, 16, 7, "f64", "aligned", "aligned", None),     # xb_wide_kernel<2, 8> (K < 128, 8 columns or fewer: no MFMA)
-    (1030, 37, 13, "f64", "eigen", "eigen", None),          # xb_wide_kernel<1, 16>
-    (1048579, 8, 6, "f32", "aligned", "aligned", None),     # xb_wide_kernel<4, 8> fp32
-    (1048576 + 37, 16, 17, "f64", "aligned", "aligned", 0),  # xb_wide_kernel<2, 20, 2>: the two-pack form (PLS_HIP_XB4=0 only)
-    (4099, 130, 45, "f64", "aligned", "aligned", None),     # xb_mfma_lds_kernel<double, 2, 3>
-    (2049, 515, 99, "f64", "aligned", "eigen", None),       # xb_mfma_lds_kernel <4> then <3>, into an unaligned out
-    (1030, 37, 42, "f32", "aligned", "aligned", None),      # xb_mfma_lds_kernel<float, 4, 2> then <1>
-    (262144 + 37, 70, 21, "f64", "aligned", "aligned", None),   # xb_mfma4_kernel resident, 6 column groups, partial last tile
-    (524288 + 5, 33, 26, "f32", "aligned", "aligned", None),    # xb_mfma4_kernel fp32 (24 columns) then xb_kernel (2)
-    (262144 + 5, 128, 3, "f64", "aligned", "aligned", None),    # xb_mfma4_kernel, the 1-4 column "few" form
-    (40001, 200, 19, "f64", "aligned", "aligned", None),        # xb_mfma4w_kernel windowed (too few tiles for the resident form)
-    (70000 + 3, 130, 18, "f32", "aligned", "aligned", None),    # xb_mfma4w_kernel fp32
-    (2000, 5000, 21, "f64", "aligned", "aligned", None),        # xb_mfma4w_kernel split over blockIdx.y + xb_split_finish_kernel
-    (1001, 9001, 5, "f64", "aligned", "eigen", None),           # ... 2 column groups, the finish into an unaligned out
-    (515, 20000, 6, "f32", "aligned", "aligned", None),         # ... fp32
-]
+# the call -> the steps xb_next (xb_route.hpp) plans for it on 256 CUs, as `kernel<selectors> (columns)`: tests/test_xb_route.py
+# checks them on the CPU
+XB_ROUTES = {
+    # N, K, C, dt, X layout, out layout, PLS_HIP_XB4
+    (600001, 16, 1, "f64", "aligned", "aligned", None): ["xb_kernel<2,1> (1)"],    # wide (>= 4 row groups per CU of 512 rows)
+    (600001, 16, 2, "f64", "aligned", "aligned", None): ["xb_kernel<2,2> (2)"],
+    (600001, 16, 3, "f64", "aligned", "aligned", None): ["xb_kernel<2,4> (3)"],
+    (600001, 16, 3, "f64", "eigen", "eigen", None): ["xb_kernel<1,4> (3)"],        # narrow
+    (1001, 37, 2, "f64", "eigen", "eigen", None): ["xb_kernel<1,2> (2)"],          # a short matrix
+    (1048579, 8, 3, "f32", "aligned", "aligned", None): ["xb_kernel<4,4> (3)"],
+    (4099, 30, 1, "f32", "eigen", "eigen", None): ["xb_kernel<1,1> (1)"],
+    (512, 20000, 1, "f64", "aligned", "aligned", None): ["xb_split<1,1> + finish (1)"],   # too few row groups for 2 rows per lane
+    (5000, 1200, 3, "f64", "aligned", "aligned", None): ["xb_split<2,4> + finish (3)"],
+    # below 32 MB: not the MFMA split; the tile of 4 columns is fixed for the call
+    (300, 9000, 6, "f64", "eigen", "eigen", None): ["xb_split<1,4> + finish (4)", "xb_split<1,4> + finish (2)"],
+    (2100, 3000, 2, "f32", "eigen", "aligned", None): ["xb_split<1,2> + finish (2)"],
+    (600001, 16, 7, "f64", "aligned", "aligned", None): ["xb_wide<2,8> (7)"],      # K < 128, 8 columns or fewer: no MFMA
+    (1030, 37, 13, "f64", "eigen", "eigen", None): ["xb_wide<1,16> (13)"],
+    (1048579, 8, 6, "f32", "aligned", "aligned", None): ["xb_wide<4,8> (6)"],
+    (1048576 + 37, 16, 17, "f64", "aligned", "aligned", 0): ["xb_wide<2,20,2> (17)"],   # the two-pack form (PLS_HIP_XB4=0 only)
+    (4099, 130, 45, "f64", "aligned", "aligned", None): ["xb_mfma_lds<2,3> (45)"],
+    (2049, 515, 99, "f64", "aligned", "eigen", None): ["xb_mfma_lds<2,4> (64)", "xb_mfma_lds<2,3> (35)"],   # into an unaligned out
+    (1030, 37, 42, "f32", "aligned", "aligned", None): ["xb_mfma_lds<4,2> (32)", "xb_mfma_lds<4,1> (10)"],
+    (262144 + 37, 70, 21, "f64", "aligned", "aligned", None): ["xb_mfma4<2,6> (21)"],   # resident, partial last tile
+    # 24 columns, then 2 on the NARROW xb_kernel: 512 row groups of 1,024 rows on 256 CUs are too few for 4 rows per lane
+    (524288 + 5, 33, 26, "f32", "aligned", "aligned", None): ["xb_mfma4<4,6> (24)", "xb_kernel<1,2> (2)"],
+    (262144 + 5, 128, 3, "f64", "aligned", "aligned", None): ["xb_mfma4<2,1> (3)"],     # the 1-4 column "few" form
+    (40001, 200, 19, "f64", "aligned", "aligned", None): ["xb_mfma4w<2,5> (19)"],       # too few tiles for the resident form
+    (70000 + 3, 130, 18, "f32", "aligned", "aligned", None): ["xb_mfma4w<4,5> (18)"],
+    (2000, 5000, 21, "f64", "aligned", "aligned", None): ["xb_mfma4w<2,6> split y=7 + finish (21)"],   # split over blockIdx.y
+    (1001, 9001, 5, "f64", "aligned", "eigen", None): ["xb_mfma4w<2,2> split y=3 + finish (5)"],   # the finish into an unaligned out
+    (515, 20000, 6, "f32", "aligned", "aligned", None): ["xb_mfma4w<4,2> split y=7 + finish (6)"],
+}
+XB_CASES = list(XB_ROUTES)
 
 
 @pytest.mark.parametrize("N,K,C,dt,xl,ol,xb4", XB_CASES)
