@@ -95,7 +95,8 @@ typedef enum { PLS_HIP_MEM_HOST = 0, PLS_HIP_MEM_DEVICE = 1 } pls_hip_mem;
  *           orthogonalises every score against the earlier ones explicitly.
  *           pls_hip_cv_folds on a handle with this option runs every fold from the same G: one sweep over X for the whole
  *           call (see there).  pls_hip_fit_batch on such a handle runs every problem from the same G: one sweep over X for
- *           Q, tt and ssy, one wide product X^T [...] per round for R and for B, any K (see there). */
+ *           Q, tt and ssy, one wide product X^T [...] per round for R and for B, any K (see there).  pls_hip_fit_resampled on
+ *           such a handle runs every row-weighted replicate (bootstrap, jack-knife) from the same G (see there). */
 typedef enum {
     PLS_HIP_ALGO_KERNEL = 0,
     PLS_HIP_ALGO_NIPALS = 1,
@@ -413,6 +414,44 @@ PLS_HIP_API int pls_hip_x_diagnostics(pls_hip_handle h, const void *X, int64_t l
 PLS_HIP_API int pls_hip_fit_batch(pls_hip_handle h, const void *X, int64_t ldx, const void *Ys, int64_t ldy,
                                   int64_t N, int64_t K, int64_t M, int64_t A, int64_t nprob, int dtype, int mem,
                                   double *R, double *Q, double *tt, double *B, double *ssy);
+
+/* ---- row-weighted replicate fits: bootstrap and jack-knife of B ------------------------------
+ * The same (X, Y) fitted under nrep sets of non-negative row weights.  Wt is N x nrep fp64, column-major with ldw >= N, and
+ * lives where `mem` says.  Replicate b is the model Model::plsr(diag(s_b) X, diag(s_b) Y, KERNEL_TYPE1) with
+ * s_b = sqrt(Wt[:, b]): a bootstrap draw is a column of integer counts, a jack-knife segment a 0/1 mask, a case-weighted fit
+ * one replicate.  The data are used as given -- no centring, the convention of pls_hip_cv_folds.
+ * Outputs, all fp64, any may be NULL (work nobody asked for beyond the component loop is not done):
+ *   Q + b*M*A (M x A) and tt + b*A      of replicate b; tt[a] = t~_a^T t~_a, the WEIGHTED sum of squares of the score
+ *   B + b*K*M (K x M, ld K)             the coefficients of replicate b, for UNSCALED rows: y^ = x^T B_b
+ *   B0 (K x M)                          the fit with unit weights, computed by the same route as a replicate: a replicate whose
+ *                                       weights are all 1 has B_b - B0 == 0 exactly
+ *   Bmean, Bm2 (K x M)                  with d_b = B_b - B0 accumulated in replicate order, s1 = sum d_b and s2 = sum d_b^2
+ *                                       (formed with fma): Bmean = B0 + s1 / nrep, Bm2 = s2 - s1^2 / nrep.
+ * The caller scales: bootstrap se = sqrt(Bm2 / (nrep - 1)), delete-a-group jack-knife over g groups se = sqrt((g - 1) / g Bm2).
+ * Rows of weight 0 drop out of the replicate.  The library does NOT inspect the weights: a negative or non-finite weight gives
+ * NaN in that replicate and in the summaries.  A replicate with fewer positively weighted rows than A has inf / NaN in its
+ * surplus columns, as a fold of pls_hip_cv_folds does.
+ * 1 <= A <= K, N >= 1, M >= 1, nrep >= 1, ldx, ldy, ldw >= N, X, Y and Wt non-NULL; anything else is PLS_HIP_ERR_INVALID.  A
+ * handle with a reducer installed returns PLS_HIP_ERR_UNSUPPORTED.  Both before anything is written.
+ * mem == DEVICE: the call only enqueues work on the handle's stream.  mem == HOST: the inputs cross through the pinned staging
+ * pipeline and the call returns with the results in place.  Fixed summation order: two calls with the same arguments return
+ * the same bits.
+ * Sample-space route (PLS_HIP_ALGO_DUAL set, N <= 8192, M <= 32, PLS_HIP_RESAMPLE_REFIT unset): G = X X^T once -- the only pass
+ * over X unless B, B0, Bmean or Bm2 is asked for.  The Gram matrix of the scaled rows is diag(s) G diag(s), so per component a
+ * round of replicates costs ONE product G [s o Y~_a of every replicate] and one workgroup per replicate that reads it back
+ * through s; B of a round is one product X^T [s o S~_b Q_b^T of every replicate], straight into the caller's array (into
+ * workspace when only a summary is wanted), and B0 one product of M columns.  Rounds hold as many replicates as 4 GB of workspace
+ * and half of the free device memory allow (3 N M + 2 N A + A^2 + M A + 2 A + 2 N values per replicate, plus K M when a summary
+ * is wanted without B; PLS_HIP_RESAMPLE_ROUND=n caps a round).  A workspace that does not fit even one replicate falls
+ * through to the general route.
+ * General route (every other handle or shape, PLS_HIP_RESAMPLE_REFIT=1): per replicate diag(s) X and diag(s) Y are written into
+ * fp64 work copies (N x K, N x M) and fitted by the handle's KERNEL_TYPE1 plan; tt comes from that fit's scores.  Shapes
+ * pls_hip_fit refuses return its status; a work copy that does not fit returns PLS_HIP_ERR_ALLOC.
+ */
+PLS_HIP_API int pls_hip_fit_resampled(pls_hip_handle h, const void *X, int64_t ldx, const void *Y, int64_t ldy,
+                                      int64_t N, int64_t K, int64_t M, int64_t A, const double *Wt, int64_t ldw,
+                                      int64_t nrep, int dtype, int mem, double *Q, double *tt, double *B, double *B0,
+                                      double *Bmean, double *Bm2);
 
 /* ---- synthetic inputs, generated on the device (DESIGN.md "Synthetic inputs") ------ */
 

@@ -135,24 +135,31 @@ __global__ __launch_bounds__(256) void dual_gy_kernel(const double *__restrict__
 // MODE = DUAL_BATCH, problem blockIdx.x of a round of pls_hip_fit_batch (dual_batch_step_kernel, dual_batch_kernels.hpp): the
 // fit's step, no mask, on the problem's slice of every array -- Ya, Z (N x M), T64, V (N x A: U only), C (A x A), Q (M x A),
 // ttv (A), scr (N + A).
+// MODE = DUAL_WEIGHTED, replicate blockIdx.x of a round of pls_hip_fit_resampled (resample_step_kernel, resample_kernels.hpp):
+// DUAL_BATCH on the row-scaled problem (diag(s) X, diag(s) Y), s = sqrt(w) the replicate's slice of sall (N).  Zall holds
+// G (s o Y_a), so the product with diag(s) G diag(s) is g = s o Z wherever Z is read; the deflation stores Y_a and, into the
+// replicate's slice of Yinall (N x M), s o Y_a -- the next product's input.
 // Stores T64[:, a] = t and ttv[a].  scr: N + A doubles (g, then c).
-enum { DUAL_FIT = 0, DUAL_CV = 1, DUAL_BATCH = 2 };
+enum { DUAL_FIT = 0, DUAL_CV = 1, DUAL_BATCH = 2, DUAL_WEIGHTED = 3 };
 template <int MODE>
 __device__ __forceinline__ void dual_step_body(const double *__restrict__ Zall, double *__restrict__ Yall, double *__restrict__ Tall,
                                                double *__restrict__ ttall, double *__restrict__ scrall, int N, int M, int A, int a,
                                                int power_iters, double *__restrict__ V, double *__restrict__ Q,
                                                double *__restrict__ C, const int *__restrict__ posall, double *__restrict__ predall,
-                                               const double *__restrict__ Y64, double *__restrict__ E, int ts, i64 fold0, i64 nobs) {
+                                               const double *__restrict__ Y64, double *__restrict__ E, int ts, i64 fold0, i64 nobs,
+                                               const double *__restrict__ sall = nullptr, double *__restrict__ Yinall = nullptr) {
     __shared__ UpdShared sh;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    constexpr bool CV = MODE == DUAL_CV;
+    constexpr bool CV = MODE == DUAL_CV, WT = MODE == DUAL_WEIGHTED;
     const i64 f = MODE != DUAL_FIT ? blockIdx.x : 0;
     const double *Z = Zall + f * M * N;
     double *Ya = Yall + f * M * N, *T64 = Tall + f * (i64)N * A, *ttv = ttall + f * A;
     double *gbuf = scrall + f * (N + A), *cbuf = gbuf + N;
     const int *pos = CV ? posall + f * N : nullptr;
     double *pred = CV ? predall + f * ts * M : nullptr;
-    if constexpr (MODE == DUAL_BATCH) {
+    const double *sv = WT ? sall + f * N : nullptr;
+    double *Yin = WT ? Yinall + f * M * N : nullptr;
+    if constexpr (MODE == DUAL_BATCH || WT) {
         V += f * N * A;
         Q += f * M * A;
         C += f * A * A;
@@ -165,7 +172,11 @@ __device__ __forceinline__ void dual_step_body(const double *__restrict__ Zall, 
             int i, j;
             tri_block(e, M, i, j);
             double s = 0.0;
-            for (int n = lane; n < N; n += 64) s = fma(Ya[n + (i64)i * N], Z[n + (i64)j * N], s);
+            if constexpr (WT) {
+                for (int n = lane; n < N; n += 64) s = fma(Ya[n + (i64)i * N], sv[n] * Z[n + (i64)j * N], s);
+            } else {
+                for (int n = lane; n < N; n += 64) s = fma(Ya[n + (i64)i * N], Z[n + (i64)j * N], s);
+            }
             s = wave_sum(s);
             if (lane == 0) sh.Gs[i + j * M] = sh.Gs[j + i * M] = s;
         }
@@ -183,11 +194,13 @@ __device__ __forceinline__ void dual_step_body(const double *__restrict__ Zall, 
             if (M > 1) {
                 for (int m = 0; m < M; ++m) {
                     u[i] = fma(Ya[n + (i64)m * N], sh.qs[m], u[i]);
-                    g[i] = fma(Z[n + (i64)m * N], sh.qs[m], g[i]);
+                    if constexpr (WT) g[i] = fma(sv[n] * Z[n + (i64)m * N], sh.qs[m], g[i]);
+                    else g[i] = fma(Z[n + (i64)m * N], sh.qs[m], g[i]);
                 }
             } else {
                 u[i] = Ya[n];
-                g[i] = Z[n];
+                if constexpr (WT) g[i] = sv[n] * Z[n];
+                else g[i] = Z[n];
             }
             gbuf[n] = g[i];
         }
@@ -234,7 +247,15 @@ __device__ __forceinline__ void dual_step_body(const double *__restrict__ Zall, 
         const int n = tid + i * UPD_THREADS;
         if (n >= N) continue;
         if (ps[i] < 0) {
-            for (int m = 0; m < M; ++m) Ya[n + (i64)m * N] = fma(-t[i], sh.qs[m], Ya[n + (i64)m * N]);
+            if constexpr (WT) {
+                for (int m = 0; m < M; ++m) {
+                    const double y = fma(-t[i], sh.qs[m], Ya[n + (i64)m * N]);
+                    Ya[n + (i64)m * N] = y;
+                    Yin[n + (i64)m * N] = sv[n] * y;
+                }
+            } else {
+                for (int m = 0; m < M; ++m) Ya[n + (i64)m * N] = fma(-t[i], sh.qs[m], Ya[n + (i64)m * N]);
+            }
             if constexpr (!CV) {
                 V[n + (i64)a * N] = u[i] / nw;
                 if constexpr (MODE == DUAL_FIT) V[n + (i64)(A + a) * N] = t[i] / tt;

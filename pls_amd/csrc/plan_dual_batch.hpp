@@ -28,11 +28,12 @@ i64 batch_dual_round_size(pls_hip_context *c, i64 N, i64 M, i64 A, i64 nprob) {
 
 // out (K x cols, ld K) = X^T V, V = N x cols (ld N): one launch of dual_xtv_kernel up to 64 columns; beyond, one launch of
 // dual_xtvb_kernel (the default) or, under PLS_HIP_DUALBATCH_SWEEPS=1, one sweep of dual_xtv_kernel per 64 columns
-// (tools/dual_batch_bench.py measures the two).  Every launch is a bracket of PLS_HIP_FAM_XTY.
+// (tools/dual_batch_bench.py measures the two).  Every launch is a bracket of PLS_HIP_FAM_XTY.  `blocks`: dual_xtvb_kernel for
+// fewer columns as well (a caller whose rounds differ in width and whose bits must not: plan_resample.hpp).
 template <typename T>
-int batch_dual_xtv(pls_hip_context *c, const T *X, i64 ldx, int N, i64 K, const double *V, int cols, double *out) {
+int batch_dual_xtv(pls_hip_context *c, const T *X, i64 ldx, int N, i64 K, const double *V, int cols, double *out, bool blocks = false) {
     const i64 es = (i64)sizeof(T);
-    if (cols > plsk::XTV_NC && !c->env.dualbatch_sweeps) {
+    if ((cols > plsk::XTV_NC || blocks) && !c->env.dualbatch_sweeps) {
         if (!plsk::raise_dynamic_lds((const void *)plsk::dual_xtvb_kernel<T>, (int)plsk::XTVB_LDS_BYTES))
             return fail(c, PLS_HIP_ERR_DEVICE, "dynamic LDS limit of the back-projection could not be raised");
         const i64 nbk = (K + plsk::XTVB_TB - 1) / plsk::XTVB_TB;

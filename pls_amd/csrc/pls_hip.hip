@@ -37,6 +37,7 @@
 #include "dual_kernels.hpp"
 #include "dual_cv_kernels.hpp"
 #include "dual_batch_kernels.hpp"
+#include "resample_kernels.hpp"
 #include "synth_kernels.hpp"
 #include "host_pipeline.hpp"
 #include "exchange_kernels.hpp"
@@ -98,6 +99,8 @@ int pls_hip_create(pls_hip_handle *out, int device, void *stream) {
         if (const char *e = getenv("PLS_HIP_BATCH_ROUND")) c->env.batch_round = atoll(e);
         if (const char *e = getenv("PLS_HIP_DUALCV_ROUND")) c->env.dualcv_round = atoll(e);
         if (const char *e = getenv("PLS_HIP_DUALBATCH_ROUND")) c->env.dualbatch_round = atoll(e);
+        if (const char *e = getenv("PLS_HIP_RESAMPLE_ROUND")) c->env.resample_round = atoll(e);
+        c->env.resample_refit = on("PLS_HIP_RESAMPLE_REFIT");
         c->env.dualbatch_sweeps = on("PLS_HIP_DUALBATCH_SWEEPS");
         c->env.tail = !off("PLS_HIP_TAIL");
         {
@@ -130,7 +133,8 @@ int pls_hip_destroy(pls_hip_handle h) {
                       &h->hT, &h->hW, &h->hP, &h->hQ, &h->hR, &h->hB, &h->hIn, &h->hOut, &h->valout, &h->valpart, &h->vale, &h->valacc, &h->valkeys,
                       &h->valhist, &h->xdS, &h->xdQ, &h->xdPT, &h->xdred, &h->xdtv, &h->xdoQ, &h->xdoT, &h->xdoS, &h->xdsmall,
                       &h->bws, &h->bv, &h->bred, &h->bmsg, &h->bssy, &h->bY, &h->boR, &h->boQ, &h->bott, &h->boB, &h->bossy,
-                      &h->dG, &h->dpart, &h->dV, &h->dT, &h->dY, &h->dZ, &h->dC, &h->dscr, &h->dcv, &h->dbat};
+                      &h->dG, &h->dpart, &h->dV, &h->dT, &h->dY, &h->dZ, &h->dC, &h->dscr, &h->dcv, &h->dbat,
+                      &h->rsw, &h->rsB, &h->rsacc, &h->rsX, &h->rsY, &h->rsW, &h->rsoS};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (void *q : h->graveyard) (void)hipFree(q);
@@ -540,6 +544,7 @@ int pls_hip_sse_by_components(pls_hip_handle h, const void *S, int64_t lds, cons
 #include "plan_dual_cv.hpp"
 #include "plan_dual_batch.hpp"
 #include "plan_batch.hpp"
+#include "plan_resample.hpp"
 
 
 extern "C" {
@@ -642,6 +647,27 @@ int pls_hip_fit_batch(pls_hip_handle h, const void *X, int64_t ldx, const void *
         return fail(h, PLS_HIP_ERR_INVALID, "bad fit_batch arguments: need N>=1, 1<=A<=K, M>=1, nprob>=1, ld>=N, X and Ys");
     CHK(set_device(h));
     return fit_batch_impl(h, X, ldx, Ys, ldy, N, K, M, A, nprob, dtype, mem, R, Q, tt, B, ssy);
+}
+
+int pls_hip_fit_resampled(pls_hip_handle h, const void *X, int64_t ldx, const void *Y, int64_t ldy, int64_t N, int64_t K, int64_t M,
+                          int64_t A, const double *Wt, int64_t ldw, int64_t nrep, int dtype, int mem, double *Q, double *tt, double *B,
+                          double *B0, double *Bmean, double *Bm2) {
+    CHK(check_handle(h));
+    if (dtype != PLS_HIP_F64 && dtype != PLS_HIP_F32) return fail(h, PLS_HIP_ERR_INVALID, "bad dtype");
+    if (mem != PLS_HIP_MEM_HOST && mem != PLS_HIP_MEM_DEVICE) return fail(h, PLS_HIP_ERR_INVALID, "bad mem kind");
+    if (N < 1 || K < 1 || M < 1 || A < 1 || A > K || nrep < 1 || K > (1 << 30) || M > (1 << 20) || nrep > (1 << 24) ||
+        nrep * M > (1 << 30) || !X || !Y || !Wt || ldx < N || ldy < N || ldw < N)
+        return fail(h, PLS_HIP_ERR_INVALID, "bad fit_resampled arguments: need N>=1, 1<=A<=K, M>=1, nrep>=1, ld>=N, X, Y and Wt");
+    if (h->reducer || h->nranks > 1)
+        return fail(h, PLS_HIP_ERR_UNSUPPORTED, "fit_resampled needs every row of X on one handle: not on a row-sharded handle");
+    // what the general route's pls_hip_fit would refuse, before anything is written
+    if (!resample_dual_covers(h, N, M)) {
+        if (M > plsk::LM_MAX) return fail(h, PLS_HIP_ERR_UNSUPPORTED, "more than 1024 responses not supported on the device");
+        if (h->opt_algo == PLS_HIP_ALGO_DUAL)
+            if (const char *why = dual_refusal(h, N, M)) return fail(h, PLS_HIP_ERR_UNSUPPORTED, why);
+    }
+    CHK(set_device(h));
+    return fit_resampled_impl(h, X, ldx, Y, ldy, N, K, M, A, Wt, ldw, nrep, dtype, mem, Q, tt, B, B0, Bmean, Bm2);
 }
 
 int pls_hip_model_sse(pls_hip_handle h, const void *X, int64_t ldx, const void *Y, int64_t ldy, int64_t N,

@@ -138,6 +138,43 @@ def _batch_view(name, a):
         return a.permute(0, 2, 1) if _is_torch(a) else a.transpose(0, 2, 1)
     return a
 
+_RESAMPLE_OUT = ("Q", "tt", "B", "B0", "Bmean", "Bm2")
+
+
+def bootstrap_weights(N: int, nrep: int, seed: int = 0):
+    """(N, nrep) fp64, column-major: column b holds the multinomial counts of one bootstrap draw of N rows out of N (how often
+    each row was drawn; every column sums to N).  Reproducible by seed.  Pure numpy, no GPU needed."""
+    rng = np.random.default_rng(seed)
+    counts = rng.multinomial(int(N), np.full(int(N), 1.0 / int(N)), size=int(nrep))
+    return np.asfortranarray(counts.T, dtype=np.float64)
+
+
+def jackknife_weights(N: int, groups=None):
+    """(N, g) fp64 0/1, column-major: column j leaves group j out.  groups=None: leave-one-out (g = N, column j drops row
+    j); otherwise an array of N group labels, the columns in the order of the sorted distinct labels."""
+    if groups is None:
+        return np.asfortranarray(1.0 - np.eye(int(N)))
+    groups = np.asarray(groups).reshape(-1)
+    if groups.shape[0] != int(N):
+        raise L.PlsHipError(L.ERR_INVALID, "jackknife_weights: one group label per row")
+    labels = np.unique(groups)
+    return np.asfortranarray((groups[:, None] != labels[None, :]).astype(np.float64))
+
+
+def resample_se(Bm2, nrep: int, kind: str = "bootstrap"):
+    """standard errors from the Bm2 = sum_b (B_b - Bbar)^2 of fit_resampled over nrep replicates: kind "bootstrap" ->
+    sqrt(Bm2 / (nrep - 1)), "jackknife" (delete-a-group over g = nrep groups) -> sqrt((g - 1) / g * Bm2).  Rounding can
+    leave Bm2 a hair below zero where the replicates agree: clamped at 0."""
+    if kind not in ("bootstrap", "jackknife"):
+        raise L.PlsHipError(L.ERR_INVALID, f"resample_se: kind={kind!r}: 'bootstrap' or 'jackknife'")
+    if kind == "bootstrap" and nrep < 2:
+        raise L.PlsHipError(L.ERR_INVALID, "resample_se: a bootstrap standard error needs nrep >= 2")
+    f = 1.0 / (nrep - 1) if kind == "bootstrap" else (nrep - 1.0) / nrep
+    if _is_torch(Bm2):
+        return torch.sqrt(torch.clamp(Bm2, min=0.0) * f)
+    return np.sqrt(np.maximum(np.asarray(Bm2, dtype=np.float64), 0.0) * f)
+
+
 # ---------------------------------------------------------------------------------------------
 # handle
 # ---------------------------------------------------------------------------------------------
@@ -500,6 +537,54 @@ class Handle:
                                          ptr("ssy"))
         L.check(rc, self.h)
         return {k: _batch_view(k, v) for k, v in out.items()}
+
+    def fit_resampled(self, X, Y, A: int, weights, want=("B0", "Bmean", "Bm2")):
+        """The same (X, Y) fitted under many sets of non-negative row weights (pls_hip_fit_resampled): weights is N x nrep,
+        replicate b the KERNEL_TYPE1 model of (diag(s) X, diag(s) Y) with s = sqrt(weights[:, b]) -- bootstrap_weights,
+        jackknife_weights, or one column of case weights.  No centring.  Returns a dict of the outputs `want` names: "Q"
+        (nrep, M, A), "tt" (nrep, A), "B" (nrep, K, M: coefficients for unscaled rows), "B0" (K, M: the unit-weight fit),
+        "Bmean" and "Bm2" (K, M: mean and sum of squared deviations of B over the replicates; resample_se scales Bm2) --
+        torch tensors on the device of X for torch inputs (the call only enqueues), numpy arrays for numpy inputs.
+        With OPT_ALGO = ALGO_DUAL (N <= 8192, M <= 32) every replicate runs from one X X^T: one sweep over X, plus one per
+        round of replicates for B; every other handle refits row-scaled copies per replicate.
+        The weights are not inspected: a negative weight gives NaN.  A handle with a reducer: PLS_HIP_ERR_UNSUPPORTED."""
+        want = set(want)
+        bad = want - set(_RESAMPLE_OUT)
+        if bad:
+            raise L.PlsHipError(L.ERR_INVALID, f"fit_resampled: unknown output(s) {sorted(bad)}")
+        if _is_torch(X):
+            X = as_colmajor(X); Y = as_colmajor(Y, X.dtype)
+            N, K = X.shape
+            M = Y.shape[1]
+            Wt = as_colmajor(torch.as_tensor(weights, device=X.device), torch.float64)
+            if Wt.shape[0] != N:
+                raise L.PlsHipError(L.ERR_INVALID, "fit_resampled: weights must have one row per row of X")
+            nrep = Wt.shape[1]
+            shp = {"Q": (nrep, A, M), "tt": (nrep, A), "B": (nrep, M, K), "B0": (M, K), "Bmean": (M, K), "Bm2": (M, K)}
+            out = {k: torch.empty(shp[k], dtype=torch.float64, device=X.device) for k in _RESAMPLE_OUT if k in want}
+            ptr = lambda k: out[k].data_ptr() if k in out else None
+            rc = self._lib.pls_hip_fit_resampled(self.h, X.data_ptr() or None, _ld(X), Y.data_ptr() or None, _ld(Y), N, K, M, A,
+                                                 Wt.data_ptr() or None, _ld(Wt), nrep, self._dt(X), L.MEM_DEVICE,
+                                                 *[ptr(k) for k in _RESAMPLE_OUT])
+            L.check(rc, self.h)
+            self._last_inputs = (X, Y, Wt)
+            return {k: (v.permute(0, 2, 1) if k in ("Q", "B") else v.t() if k != "tt" else v) for k, v in out.items()}
+        dt = np.float32 if np.asarray(X).dtype == np.float32 else np.float64
+        X = _np_f(X, dt); Y = _np_f(Y, dt)
+        Wt = _np_f(weights, np.float64)
+        N, K = X.shape
+        M = Y.shape[1]
+        if Wt.shape[0] != N:
+            raise L.PlsHipError(L.ERR_INVALID, "fit_resampled: weights must have one row per row of X")
+        nrep = Wt.shape[1]
+        shp = {"Q": (nrep, A, M), "tt": (nrep, A), "B": (nrep, M, K), "B0": (M, K), "Bmean": (M, K), "Bm2": (M, K)}
+        out = {k: np.zeros(shp[k]) for k in _RESAMPLE_OUT if k in want}
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        ptr = lambda k: p(out[k]) if k in out else None
+        rc = self._lib.pls_hip_fit_resampled(self.h, p(X), max(N, 1), p(Y), max(N, 1), N, K, M, A, p(Wt), max(N, 1), nrep,
+                                             L.F64 if dt == np.float64 else L.F32, L.MEM_HOST, *[ptr(k) for k in _RESAMPLE_OUT])
+        L.check(rc, self.h)
+        return {k: (v.transpose(0, 2, 1) if k in ("Q", "B") else v.T if k != "tt" else v) for k, v in out.items()}
 
     def permutation_test(self, X, Y, A: int, nperm: int, perms=None, seed: int = 0, max_bytes: int = 1 << 30):
         """Response-permutation (Y-randomisation) test: problem 0 is Y itself, problem b is Y[perms[b-1]] (rows permuted,
@@ -945,6 +1030,22 @@ class Model:
         """Handle.permutation_test on the model's own training data with the model's number of components: is the R^2 Y
         of this model better than what the same X explains of row-permuted responses?"""
         return self.handle.permutation_test(self._X, self._Y, self.A, nperm, perms=perms, seed=seed, max_bytes=max_bytes)
+
+    def _resample(self, Wt, kind):
+        o = self.handle.fit_resampled(self._X, self._Y, self.A, Wt, want=("B0", "Bmean", "Bm2"))
+        return dict(B0=o["B0"], Bmean=o["Bmean"], se=resample_se(o["Bm2"], Wt.shape[1], kind))
+
+    def bootstrap(self, nrep: int, seed: int = 0):
+        """dict(B0, Bmean, se), each K x M: the coefficients of the model's training data, their mean over nrep bootstrap
+        draws of its rows (bootstrap_weights(N, nrep, seed)) and the bootstrap standard error of every coefficient, with
+        the model's number of components.  Under ALGO_DUAL every draw runs from one X X^T (Handle.fit_resampled)."""
+        return self._resample(bootstrap_weights(self._X.shape[0], nrep, seed), "bootstrap")
+
+    def jackknife(self, groups=None):
+        """dict(B0, Bmean, se), each K x M: the delete-a-group jack-knife of the coefficients over the cross-validation
+        segments (Martens' uncertainty test) -- leave-one-out by default, otherwise an array of N group labels
+        (jackknife_weights)."""
+        return self._resample(jackknife_weights(self._X.shape[0], groups), "jackknife")
 
     def explained_variance_by_components(self, X, Y):
         """(EV, SSE), each M x A: what print_explained_variance (src/pls.cpp:551-562) reports for
