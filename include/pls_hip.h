@@ -96,7 +96,9 @@ typedef enum { PLS_HIP_MEM_HOST = 0, PLS_HIP_MEM_DEVICE = 1 } pls_hip_mem;
  *           pls_hip_cv_folds on a handle with this option runs every fold from the same G: one sweep over X for the whole
  *           call (see there).  pls_hip_fit_batch on such a handle runs every problem from the same G: one sweep over X for
  *           Q, tt and ssy, one wide product X^T [...] per round for R and for B, any K (see there).  pls_hip_fit_resampled on
- *           such a handle runs every row-weighted replicate (bootstrap, jack-knife) from the same G (see there). */
+ *           such a handle runs every row-weighted replicate (bootstrap, jack-knife) from the same G (see there).
+ *           pls_hip_cv_press_batch on such a handle runs the cross-validation folds of every problem from the same G and
+ *           reduces PRESS on the device: one sweep over X for a whole Q^2 permutation test (see there). */
 typedef enum {
     PLS_HIP_ALGO_KERNEL = 0,
     PLS_HIP_ALGO_NIPALS = 1,
@@ -452,6 +454,40 @@ PLS_HIP_API int pls_hip_fit_resampled(pls_hip_handle h, const void *X, int64_t l
                                       int64_t N, int64_t K, int64_t M, int64_t A, const double *Wt, int64_t ldw,
                                       int64_t nrep, int dtype, int mem, double *Q, double *tt, double *B, double *B0,
                                       double *Bmean, double *Bm2);
+
+/* ---- cross-validated fits of many response sets: PRESS per problem, the Q^2 permutation test ----
+ * The cross-validation of pls_hip_cv_folds for nprob response sets against one X, reduced to what a Q^2 needs.  Ys is as in
+ * pls_hip_fit_batch (N x nprob*M, problem b owns the columns [b*M, (b+1)*M)); test_idx (HOST memory), test_size and num_folds
+ * are as in pls_hip_cv_folds, nobs = num_folds * test_size, and the same folds apply to every problem.  The data are used as
+ * given -- no centring.
+ * Outputs, all fp64, living where `mem` says, any may be NULL:
+ *   PRESS + b*M*A (M x A, ld M)   PRESS[m + c*M] = sum over o < nobs of E_b[m][o, c]^2
+ *   ssy + b*M (M)                 ssy[m] = sum over o < nobs of Y_b[row(o), m]^2: the PRESS of the zero-component model over the
+ *                                 same observations (a row held out twice counts twice), so Q^2[m, c] = 1 - PRESS / ssy
+ *   E + b*M*nobs*A                exactly what pls_hip_cv_folds(X, Y_b, ...) documents, for problem b.  Normally NULL: nothing
+ *                                 nobs x A-sized per problem then exists anywhere.
+ * The checks of pls_hip_cv_folds, nprob >= 1 and Ys non-NULL; anything else is PLS_HIP_ERR_INVALID.  A handle with a reducer
+ * installed returns PLS_HIP_ERR_UNSUPPORTED.  Both before anything is written.  The call returns after the work has completed.
+ * Fixed summation order, no atomics: two calls with the same arguments return the same bits, and PRESS and ssy have the same
+ * bits whether or not E is asked for.
+ * Sample-space route (the conditions of pls_hip_cv_folds under PLS_HIP_ALGO_DUAL, and PLS_HIP_CVBATCH_REFIT unset): G = X X^T
+ * once -- the only pass over X whatever A, nprob and num_folds are.  The work items are the pairs item = b*num_folds + f, in
+ * that order, in rounds of as many as 4 GB of workspace and half of the free device memory hold (2 N M + N A + N + 2 A +
+ * 3 test_size M + M A + M values per item, fewer than 2^30 / (N M) items; PLS_HIP_DUALCVB_ROUND=n caps a round); a problem's
+ * folds may straddle two rounds.  The training-row masks exist once per fold (N ints each), shared by the problems.  Per
+ * component a round costs one product G [Y_a of every item] and one workgroup per item, which leaves the item's partial PRESS
+ * summed over its held-out rows by test position; after the round the partials are added to PRESS_b in item order, so every
+ * (b, m, c) adds its folds in fold order wherever the round boundaries fall.  ssy likewise.  The columns of Ys are converted to
+ * fp64 round by round.  A workspace that does not fit even one item falls through to the general route.
+ * General route (every other handle or shape, PLS_HIP_CVBATCH_REFIT=1): per problem pls_hip_cv_folds on (X, Y_b) -- into the
+ * caller's slice of E or a workspace of M nobs A doubles -- then the PRESS kernels of pls_hip_validation; a small kernel for
+ * ssy.  The same results to rounding at the cost of nprob cross-validations; statuses of pls_hip_cv_folds are passed on, and
+ * PRESS there needs nobs < 2^31, M A <= 2^24 (PLS_HIP_ERR_UNSUPPORTED otherwise).
+ */
+PLS_HIP_API int pls_hip_cv_press_batch(pls_hip_handle h, const void *X, int64_t ldx, const void *Ys, int64_t ldy,
+                                       int64_t N, int64_t K, int64_t M, int64_t A, int64_t nprob,
+                                       const int64_t *test_idx, int64_t test_size, int64_t num_folds, int dtype, int mem,
+                                       double *PRESS, double *ssy, double *E);
 
 /* ---- synthetic inputs, generated on the device (DESIGN.md "Synthetic inputs") ------ */
 

@@ -80,6 +80,8 @@ PROTOTYPES = [
     ("pls_hip_fit_batch", _int, [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     ("pls_hip_fit_resampled", _int, [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _int, _int,
                                      _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("pls_hip_cv_press_batch", _int, [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _int, _int,
+                                      _vp, _vp, _vp]),
     ("pls_hip_synth_x", _int, [_vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_uint64, _int]),
     ("pls_hip_synth_y", _int, [_vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_uint64, _int]),
     # one process, several GPUs: groups and resident matrices

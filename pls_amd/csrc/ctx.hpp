@@ -37,6 +37,7 @@ struct pls_hip_context {
     DevBuf dG, dpart, dV, dT, dY, dZ, dC, dscr;  // PLS_HIP_ALGO_DUAL (plan_dual.hpp): X X^T, its split partials, [U | T / tt], the fp64 scores, Y_a, G Y_a, C, small vectors
     DevBuf dcv;  // its cross-validation folds (plan_dual_cv.hpp): the state of a round's folds
     DevBuf dbat;  // its batched fits (plan_dual_batch.hpp): the state of a round's problems
+    DevBuf dcvb, cvbpos, cvbidx, cvbo, cvboE;  // pls_hip_cv_press_batch (plan_dual_cvbatch.hpp): the state of a round's items, pos of every fold, the test rows, host staging of [PRESS | ssy] and of E
     DevBuf rsw, rsB, rsacc, rsX, rsY, rsW, rsoS;  // pls_hip_fit_resampled (plan_resample.hpp): the state of a round's replicates (general route: of one fit), a round's B, [s1, s2, B0], the row-scaled work copies, host staging of the weights and of [B0, Bmean, Bm2]
     i64 opt_val_lds_rows = -1;  // PLS_HIP_OPT_VALIDATION_LDS_ROWS; -1 = the device's own limit
     i64 val_lds_rows_dev = -1;  // that limit, found on first use
@@ -99,6 +100,10 @@ struct pls_hip_context {
     //   PLS_HIP_RESAMPLE_REFIT=1 pls_hip_fit_resampled as one KERNEL_TYPE1 fit per replicate on row-scaled copies (the general form;
     //                            tests compare)
     //   PLS_HIP_RESAMPLE_ROUND=n at most n replicates per round of pls_hip_fit_resampled under PLS_HIP_ALGO_DUAL (tests: several rounds)
+    //   PLS_HIP_CVBATCH_REFIT=1  pls_hip_cv_press_batch as one pls_hip_cv_folds plus the PRESS kernels of pls_hip_validation per
+    //                            problem (the general form; tests compare)
+    //   PLS_HIP_DUALCVB_ROUND=n  at most n (problem, fold) pairs per round of pls_hip_cv_press_batch under PLS_HIP_ALGO_DUAL
+    //                            (tests: several rounds)
     //   PLS_HIP_RESIDENT=0       mid-size single-response fits on the general plan instead of the one-launch resident fit
     //   PLS_HIP_REPLICA_GUARD=0  no replica-divergence check after a sharded fit (must be the same on every rank)
     //   PLS_HIP_TURNAROUND=0     every fused pass walks ascending with the nt policy throughout (A/B measurements; must be the
@@ -113,6 +118,8 @@ struct pls_hip_context {
         i64 resample_round = 0;
         bool resample_refit = false;
         bool dualbatch_sweeps = false;
+        bool cvbatch_refit = false;
+        i64 dualcvb_round = 0;
         bool tiny = true, cv_refit = false, tail = true, replica_guard = true, resident = true;
         int tail_update = 1;  // 0: never, 1: in the tail of READ-ONLY passes (default), 2: of every pass
         int xb4 = 1;          // PLS_HIP_XB4=0: X B with 5..32 columns on the older kernels

@@ -7,8 +7,9 @@
 //   dual_gy_kernel        Z = G Y_a (N x M): one wave per column of the symmetric G, the whole chip
 //   dual_step_kernel      everything else of a component, N (M + a) work, ONE workgroup: direction, norm, orthogonalisation
 //                         of the score against the earlier ones, loading of Y, deflation of Y_a (dual_step_body, which the
-//                         cross-validation folds of dual_cv_kernels.hpp run with their training-row masks and the batched fits
-//                         of dual_batch_kernels.hpp per problem)
+//                         cross-validation folds of dual_cv_kernels.hpp run with their training-row masks, the batched fits
+//                         of dual_batch_kernels.hpp per problem and the cross-validated batches of dual_cvbatch_kernels.hpp
+//                         per (problem, fold) pair)
 //   dual_xtv_kernel       [W | P] = X^T [U | T diag(1/tt)], up to 64 columns per sweep over X, on the matrix cores
 //   dual_r_kernel         r_a = w_a - sum_{j<a} C[j, a] r_j, a thread per row of R
 //   dual_convert_kernel   Y -> fp64 working copy, fp64 scores -> T in the storage type
@@ -139,23 +140,32 @@ __global__ __launch_bounds__(256) void dual_gy_kernel(const double *__restrict__
 // DUAL_BATCH on the row-scaled problem (diag(s) X, diag(s) Y), s = sqrt(w) the replicate's slice of sall (N).  Zall holds
 // G (s o Y_a), so the product with diag(s) G diag(s) is g = s o Z wherever Z is read; the deflation stores Y_a and, into the
 // replicate's slice of Yinall (N x M), s o Y_a -- the next product's input.
+// MODE = DUAL_CVB, item fold0 + blockIdx.x of a round of pls_hip_cv_press_batch (dual_cvb_step_kernel, dual_cvbatch_kernels.hpp;
+// fold0 carries the round's first item): DUAL_CV on the pair (problem item / nfolds, fold item % nfolds).  pos (N per FOLD of the
+// call) is indexed by the fold and shared by the problems; Y64 holds the responses of the item's held-out rows (ts x M per item);
+// E (null: not asked for) is indexed by the problem.  The residual of a held-out row also goes to the item's slice of escr
+// (ts x M) at the row's TEST POSITION, and one wave per response then sums their squares over the positions in a fixed order
+// into press[m + a M] of the item (M x A per item): the sum does not depend on which thread owns which row.
 // Stores T64[:, a] = t and ttv[a].  scr: N + A doubles (g, then c).
-enum { DUAL_FIT = 0, DUAL_CV = 1, DUAL_BATCH = 2, DUAL_WEIGHTED = 3 };
+enum { DUAL_FIT = 0, DUAL_CV = 1, DUAL_BATCH = 2, DUAL_WEIGHTED = 3, DUAL_CVB = 4 };
 template <int MODE>
 __device__ __forceinline__ void dual_step_body(const double *__restrict__ Zall, double *__restrict__ Yall, double *__restrict__ Tall,
                                                double *__restrict__ ttall, double *__restrict__ scrall, int N, int M, int A, int a,
                                                int power_iters, double *__restrict__ V, double *__restrict__ Q,
                                                double *__restrict__ C, const int *__restrict__ posall, double *__restrict__ predall,
                                                const double *__restrict__ Y64, double *__restrict__ E, int ts, i64 fold0, i64 nobs,
-                                               const double *__restrict__ sall = nullptr, double *__restrict__ Yinall = nullptr) {
+                                               const double *__restrict__ sall = nullptr, double *__restrict__ Yinall = nullptr,
+                                               i64 nfolds = 1, double *__restrict__ escrall = nullptr,
+                                               double *__restrict__ pressall = nullptr) {
     __shared__ UpdShared sh;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    constexpr bool CV = MODE == DUAL_CV, WT = MODE == DUAL_WEIGHTED;
+    constexpr bool CVB = MODE == DUAL_CVB, CV = MODE == DUAL_CV || CVB, WT = MODE == DUAL_WEIGHTED;
     const i64 f = MODE != DUAL_FIT ? blockIdx.x : 0;
     const double *Z = Zall + f * M * N;
     double *Ya = Yall + f * M * N, *T64 = Tall + f * (i64)N * A, *ttv = ttall + f * A;
     double *gbuf = scrall + f * (N + A), *cbuf = gbuf + N;
-    const int *pos = CV ? posall + f * N : nullptr;
+    const i64 prob = CVB ? (fold0 + f) / nfolds : 0, fold = CVB ? (fold0 + f) % nfolds : fold0 + f;  // (CV)
+    const int *pos = CV ? posall + (CVB ? fold : f) * N : nullptr;
     double *pred = CV ? predall + f * ts * M : nullptr;
     const double *sv = WT ? sall + f * N : nullptr;
     double *Yin = WT ? Yinall + f * M * N : nullptr;
@@ -261,12 +271,28 @@ __device__ __forceinline__ void dual_step_body(const double *__restrict__ Zall, 
                 if constexpr (MODE == DUAL_FIT) V[n + (i64)(A + a) * N] = t[i] / tt;
             }
         } else {
-            double *e = E + (i64)a * nobs + (fold0 + f) * ts + ps[i];
+            double *e = E + (prob * M * A + a) * nobs + fold * ts + ps[i];
             for (int m = 0; m < M; ++m) {
                 const double p = fma(t[i], sh.qs[m], pred[ps[i] + (i64)m * ts]);
                 pred[ps[i] + (i64)m * ts] = p;
-                e[(i64)m * nobs * A] = Y64[n + (i64)m * N] - p;
+                if constexpr (CVB) {
+                    const double r = Y64[(f * M + m) * ts + ps[i]] - p;
+                    escrall[(f * M + m) * ts + ps[i]] = r;
+                    if (E) e[(i64)m * nobs * A] = r;
+                } else {
+                    e[(i64)m * nobs * A] = Y64[n + (i64)m * N] - p;
+                }
             }
+        }
+    }
+    if constexpr (CVB) {
+        __syncthreads();  // (publishes escr)
+        for (int m = wv; m < M; m += UPD_WAVES) {  // a wave per response: the held-out rows by test position
+            const double *r = escrall + (f * M + m) * ts;
+            double s = 0.0;
+            for (int i = lane; i < ts; i += 64) s = fma(r[i], r[i], s);
+            s = wave_sum(s);
+            if (lane == 0) pressall[f * M * A + m + (i64)a * M] = s;
         }
     }
 }

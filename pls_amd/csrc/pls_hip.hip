@@ -37,6 +37,7 @@
 #include "dual_kernels.hpp"
 #include "dual_cv_kernels.hpp"
 #include "dual_batch_kernels.hpp"
+#include "dual_cvbatch_kernels.hpp"
 #include "resample_kernels.hpp"
 #include "synth_kernels.hpp"
 #include "host_pipeline.hpp"
@@ -102,6 +103,8 @@ int pls_hip_create(pls_hip_handle *out, int device, void *stream) {
         if (const char *e = getenv("PLS_HIP_RESAMPLE_ROUND")) c->env.resample_round = atoll(e);
         c->env.resample_refit = on("PLS_HIP_RESAMPLE_REFIT");
         c->env.dualbatch_sweeps = on("PLS_HIP_DUALBATCH_SWEEPS");
+        c->env.cvbatch_refit = on("PLS_HIP_CVBATCH_REFIT");
+        if (const char *e = getenv("PLS_HIP_DUALCVB_ROUND")) c->env.dualcvb_round = atoll(e);
         c->env.tail = !off("PLS_HIP_TAIL");
         {
             const char *e = getenv("PLS_HIP_TAIL");
@@ -134,6 +137,7 @@ int pls_hip_destroy(pls_hip_handle h) {
                       &h->valhist, &h->xdS, &h->xdQ, &h->xdPT, &h->xdred, &h->xdtv, &h->xdoQ, &h->xdoT, &h->xdoS, &h->xdsmall,
                       &h->bws, &h->bv, &h->bred, &h->bmsg, &h->bssy, &h->bY, &h->boR, &h->boQ, &h->bott, &h->boB, &h->bossy,
                       &h->dG, &h->dpart, &h->dV, &h->dT, &h->dY, &h->dZ, &h->dC, &h->dscr, &h->dcv, &h->dbat,
+                      &h->dcvb, &h->cvbpos, &h->cvbidx, &h->cvbo, &h->cvboE,
                       &h->rsw, &h->rsB, &h->rsacc, &h->rsX, &h->rsY, &h->rsW, &h->rsoS};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
@@ -545,6 +549,7 @@ int pls_hip_sse_by_components(pls_hip_handle h, const void *S, int64_t lds, cons
 #include "plan_dual_batch.hpp"
 #include "plan_batch.hpp"
 #include "plan_resample.hpp"
+#include "plan_dual_cvbatch.hpp"
 
 
 extern "C" {
@@ -668,6 +673,26 @@ int pls_hip_fit_resampled(pls_hip_handle h, const void *X, int64_t ldx, const vo
     }
     CHK(set_device(h));
     return fit_resampled_impl(h, X, ldx, Y, ldy, N, K, M, A, Wt, ldw, nrep, dtype, mem, Q, tt, B, B0, Bmean, Bm2);
+}
+
+int pls_hip_cv_press_batch(pls_hip_handle h, const void *X, int64_t ldx, const void *Ys, int64_t ldy, int64_t N, int64_t K, int64_t M,
+                           int64_t A, int64_t nprob, const int64_t *test_idx, int64_t test_size, int64_t num_folds, int dtype, int mem,
+                           double *PRESS, double *ssy, double *E) {
+    CHK(check_handle(h));
+    if (dtype != PLS_HIP_F64 && dtype != PLS_HIP_F32) return fail(h, PLS_HIP_ERR_INVALID, "bad dtype");
+    if (mem != PLS_HIP_MEM_HOST && mem != PLS_HIP_MEM_DEVICE) return fail(h, PLS_HIP_ERR_INVALID, "bad mem kind");
+    if (N < 2 || K < 1 || M < 1 || A < 1 || A > K || K > (1 << 30) || nprob < 1 || nprob > (1 << 24) || nprob * M > (1 << 30) || !X ||
+        !Ys || !test_idx || test_size < 1 || test_size >= N || num_folds < 1 || ldx < N || ldy < N || num_folds > (1 << 22) ||
+        test_size > (1 << 20))
+        return fail(h, PLS_HIP_ERR_INVALID, "bad cv_press_batch arguments: need N>=2, 1<=A<=K, M>=1, nprob>=1, 1<=test_size<N, ld>=N, X, Ys and test_idx");
+    const i64 nobs = num_folds * test_size;
+    for (i64 j = 0; j < nobs; ++j)
+        if (test_idx[j] < 0 || test_idx[j] >= N) return fail(h, PLS_HIP_ERR_INVALID, "cv_press_batch: test index out of range");
+    if (h->reducer || h->nranks > 1)
+        return fail(h, PLS_HIP_ERR_UNSUPPORTED, "cv_press_batch needs every row of X on one handle: not on a row-sharded handle");
+    if (M > plsk::LM_MAX) return fail(h, PLS_HIP_ERR_UNSUPPORTED, "more than 1024 responses not supported on the device");
+    CHK(set_device(h));
+    return cv_press_batch_impl(h, X, ldx, Ys, ldy, N, K, M, A, nprob, test_idx, test_size, num_folds, dtype, mem, PRESS, ssy, E);
 }
 
 int pls_hip_model_sse(pls_hip_handle h, const void *X, int64_t ldx, const void *Y, int64_t ldy, int64_t N,

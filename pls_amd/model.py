@@ -106,6 +106,15 @@ def r2y_by_components(Q, tt, ssy):
     return np.cumsum(Q * Q * tt, axis=2) / ssy
 
 
+def q2_by_components(PRESS, ssy):
+    """Cross-validated Q^2 Y from the outputs of cv_press_batch: PRESS (nprob, M, A), ssy (nprob, M) -> (nprob, M, A) with
+    Q2[b, m, c] = 1 - PRESS[b, m, c] / ssy[b, m].  Pure array code: numpy arrays or torch tensors, no GPU needed."""
+    if _is_torch(PRESS):
+        return 1.0 - PRESS / ssy.reshape(PRESS.shape[0], PRESS.shape[1], 1)
+    PRESS = np.asarray(PRESS, dtype=np.float64)
+    return 1.0 - PRESS / np.asarray(ssy, dtype=np.float64).reshape(PRESS.shape[0], PRESS.shape[1], 1)
+
+
 def permutation_pvalues(r2_real, r2_perm):
     """(1 + #{b : r2_perm[b] >= r2_real}) / (nperm + 1), elementwise over (M, A): the permutation p-value of every
     (response, component count) with the real model counted among the permutations.  r2_perm: (nperm, M, A)."""
@@ -139,6 +148,7 @@ def _batch_view(name, a):
     return a
 
 _RESAMPLE_OUT = ("Q", "tt", "B", "B0", "Bmean", "Bm2")
+_CVB_OUT = ("PRESS", "ssy", "E")
 
 
 def bootstrap_weights(N: int, nrep: int, seed: int = 0):
@@ -586,12 +596,65 @@ class Handle:
         L.check(rc, self.h)
         return {k: (v.transpose(0, 2, 1) if k in ("Q", "B") else v.T if k != "tt" else v) for k, v in out.items()}
 
-    def permutation_test(self, X, Y, A: int, nperm: int, perms=None, seed: int = 0, max_bytes: int = 1 << 30):
+    def cv_press_batch(self, X, Ys, M: int, A: int, test_idx, want=("PRESS", "ssy")):
+        """Cross-validated fits of many response sets against one X, reduced to PRESS (pls_hip_cv_press_batch): Ys is
+        N x (nprob * M) as in fit_batch, test_idx (num_folds, test_size) as in cv_folds, the same folds for every problem.
+        Returns a dict of the outputs `want` names: "PRESS" (nprob, M, A) = the column sums of squares of the problem's
+        cross-validation residuals, "ssy" (nprob, M) = the sum of squares of the responses over the same held-out
+        observations (q2_by_components: Q^2 = 1 - PRESS / ssy), "E" (nprob, M, nobs, A) = the residuals themselves, what
+        cv_folds returns per problem -- torch tensors on the device of X for torch inputs, numpy arrays for numpy inputs.
+        The call returns after the work has completed.
+        With OPT_ALGO = ALGO_DUAL (no reducer, N <= 8192, M <= 32) every problem and fold runs from one G = X X^T: one sweep
+        over X for the whole call; every other handle runs one cross-validation per problem.
+        A handle with a reducer: PLS_HIP_ERR_UNSUPPORTED."""
+        want = set(want)
+        bad = want - set(_CVB_OUT)
+        if bad:
+            raise L.PlsHipError(L.ERR_INVALID, f"cv_press_batch: unknown output(s) {sorted(bad)}")
+        idx = np.ascontiguousarray(np.asarray(test_idx, dtype=np.int64))
+        if idx.ndim == 1:
+            idx = idx[:, None]
+        nf, ts = idx.shape
+        on_dev = _is_torch(X)
+        if on_dev:
+            X = as_colmajor(X); Ys = as_colmajor(Ys, X.dtype)
+        else:
+            dt = np.float32 if np.asarray(X).dtype == np.float32 else np.float64
+            X = _np_f(X, dt); Ys = _np_f(Ys, dt)
+        N, K = X.shape
+        C = Ys.shape[1]
+        if M < 1 or C % M:
+            raise L.PlsHipError(L.ERR_INVALID, "cv_press_batch: the columns of Ys are not a multiple of M")
+        nprob = C // M
+        # every problem's block in the library's layout (M x A ld M; M matrices of nobs x A) inside a C-ordered stack
+        shp = {"PRESS": (nprob, A, M), "ssy": (nprob, M), "E": (nprob, M, A, nf * ts)}
+        view = {"PRESS": (0, 2, 1), "ssy": (0, 1), "E": (0, 1, 3, 2)}
+        if on_dev:
+            out = {k: torch.empty(shp[k], dtype=torch.float64, device=X.device) for k in _CVB_OUT if k in want}
+            ptr = lambda k: out[k].data_ptr() if k in out else None
+            rc = self._lib.pls_hip_cv_press_batch(self.h, X.data_ptr() or None, _ld(X), Ys.data_ptr() or None, _ld(Ys), N, K, M, A,
+                                                  nprob, idx.ctypes.data_as(ctypes.c_void_p), ts, nf, self._dt(X), L.MEM_DEVICE,
+                                                  *[ptr(k) for k in _CVB_OUT])
+            L.check(rc, self.h)
+            return {k: v.permute(*view[k]) for k, v in out.items()}
+        out = {k: np.zeros(shp[k]) for k in _CVB_OUT if k in want}
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        ptr = lambda k: p(out[k]) if k in out else None
+        rc = self._lib.pls_hip_cv_press_batch(self.h, p(X), max(N, 1), p(Ys), max(N, 1), N, K, M, A, nprob, p(idx), ts, nf,
+                                              L.F64 if dt == np.float64 else L.F32, L.MEM_HOST, *[ptr(k) for k in _CVB_OUT])
+        L.check(rc, self.h)
+        return {k: v.transpose(*view[k]) for k, v in out.items()}
+
+    def permutation_test(self, X, Y, A: int, nperm: int, perms=None, seed: int = 0, max_bytes: int = 1 << 30, cv=None):
         """Response-permutation (Y-randomisation) test: problem 0 is Y itself, problem b is Y[perms[b-1]] (rows permuted,
         the M responses of a row together), all fitted against the same X by fit_batch.  perms: (nperm, N) int64; drawn
         with numpy.random.default_rng(seed).permutation when not given.  The rows are gathered by the array library where
         the data lives, in chunks whose Ys stays under max_bytes.  Returns dict(r2y (M, A), r2y_perm (nperm, M, A),
         p (M, A), perms): cumulative R^2 Y per component count, and p = (1 + #{perm >= real}) / (nperm + 1).
+        cv: an index array (num_folds, test_size) of held-out rows as cv_folds takes it -- the test then also cross-validates
+        every problem over these folds (cv_press_batch, chunk by chunk on the same Ys) and the result gains q2y (M, A),
+        q2y_perm (nperm, M, A) and p_q2: Q^2 Y = 1 - PRESS / ssy per component count and its permutation p-value.  R^2 Y of a
+        model with many predictors is close to 1 under permutation too; Q^2 Y is the figure to read.
         A handle with a reducer raises ValueError: a permutation moves rows across ranks -- sharded callers build Ys
         themselves and call fit_batch."""
         if self._has_reducer():
@@ -611,7 +674,7 @@ class Handle:
         nperm = perms.shape[0]
         es = 4 if (Y2.dtype == (torch.float32 if on_dev else np.float32)) else 8
         chunk = max(1, int(max_bytes) // max(1, N * M * es))
-        r2 = []
+        r2, q2 = [], []
         for b0 in range(0, nperm + 1, chunk):  # problem index 0 = the identity
             b1 = min(nperm + 1, b0 + chunk)
             rows = [np.arange(N, dtype=np.int64)] if b0 == 0 else []
@@ -627,8 +690,16 @@ class Handle:
             o = self.fit_batch(X, Ys, M, A, want=("Q", "tt", "ssy"))
             part = r2y_by_components(o["Q"], o["tt"], o["ssy"])
             r2.append(part.cpu().numpy() if on_dev else part)
+            if cv is not None:
+                o = self.cv_press_batch(X, Ys, M, A, cv, want=("PRESS", "ssy"))
+                part = q2_by_components(o["PRESS"], o["ssy"])
+                q2.append(part.cpu().numpy() if on_dev else part)
         r2 = np.concatenate(r2, axis=0)
-        return dict(r2y=r2[0], r2y_perm=r2[1:], p=permutation_pvalues(r2[0], r2[1:]), perms=perms)
+        res = dict(r2y=r2[0], r2y_perm=r2[1:], p=permutation_pvalues(r2[0], r2[1:]), perms=perms)
+        if cv is not None:
+            q2 = np.concatenate(q2, axis=0)
+            res.update(q2y=q2[0], q2y_perm=q2[1:], p_q2=permutation_pvalues(q2[0], q2[1:]))
+        return res
 
     def _has_reducer(self) -> bool:
         on, rank, n = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
@@ -1026,10 +1097,11 @@ class Model:
         ssx = out["ssx"]
         return dict(Q=out["Q"], T2=out["T2"], R2X=1.0 - ssx[1:] / ssx[0])
 
-    def permutation_test(self, nperm: int, perms=None, seed: int = 0, max_bytes: int = 1 << 30):
+    def permutation_test(self, nperm: int, perms=None, seed: int = 0, max_bytes: int = 1 << 30, cv=None):
         """Handle.permutation_test on the model's own training data with the model's number of components: is the R^2 Y
-        of this model better than what the same X explains of row-permuted responses?"""
-        return self.handle.permutation_test(self._X, self._Y, self.A, nperm, perms=perms, seed=seed, max_bytes=max_bytes)
+        of this model better than what the same X explains of row-permuted responses?  cv (num_folds, test_size): the
+        cross-validated Q^2 Y of the real and the permuted models as well (q2y, q2y_perm, p_q2)."""
+        return self.handle.permutation_test(self._X, self._Y, self.A, nperm, perms=perms, seed=seed, max_bytes=max_bytes, cv=cv)
 
     def _resample(self, Wt, kind):
         o = self.handle.fit_resampled(self._X, self._Y, self.A, Wt, want=("B0", "Bmean", "Bm2"))
