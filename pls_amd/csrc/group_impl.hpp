@@ -586,14 +586,12 @@ int pls_hip_group_upload_xy(pls_hip_group g, const void *hostX, int64_t ldx, con
             HIPCHK(c, hipMemsetAsync(X->gram_xx[r], 0, (size_t)K * K * 8, c->stream));
             HIPCHK(c, hipMemsetAsync(X->gram_xy[r], 0, (size_t)K * M * 8, c->stream));
             ok = true;
-        } else if (dtype == PLS_HIP_F64) {
-            CHK(upload_accumulate<double>(c, (double *)X->data[r], X->ld[r], (const double *)hostX + X->row0[r], ldx,
-                                          X->nrows[r], (int)K, (const double *)Y->data[r], Y->ld[r], (int)M,
-                                          X->gram_xx[r], X->gram_xy[r], &ok));
         } else {
-            CHK(upload_accumulate<float>(c, (float *)X->data[r], X->ld[r], (const float *)hostX + X->row0[r], ldx,
-                                         X->nrows[r], (int)K, (const float *)Y->data[r], Y->ld[r], (int)M, X->gram_xx[r],
-                                         X->gram_xy[r], &ok));
+            CHK(by_dtype(dtype, [&](auto t) {
+                using T = decltype(t);
+                return upload_accumulate<T>(c, (T *)X->data[r], X->ld[r], (const T *)hostX + X->row0[r], ldx, X->nrows[r], (int)K,
+                                            (const T *)Y->data[r], Y->ld[r], (int)M, X->gram_xx[r], X->gram_xy[r], &ok);
+            }));
         }
         okv[r] = ok ? 1 : 0;
         HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller's memory has been read, the products are complete

@@ -1,4 +1,4 @@
-// host_entry.hpp -- handle checks, fit timing brackets, host <-> device staging and the upload that accumulates X^T X / X^T Y on the way.
+// host_entry.hpp -- handle checks, fit timing brackets, host <-> device staging (h2d, d2h, HostOutputs) and the upload that accumulates X^T X / X^T Y on the way.
 // Part of libpls_hip.so: included by pls_hip.hip (one translation unit), in the order given there.
 #pragma once
 
@@ -54,6 +54,39 @@ int d2h(pls_hip_context *c, void *dst, i64 ldd, const void *src, i64 lds, i64 ro
                                (size_t)cols, hipMemcpyDeviceToHost, c->stream));
     return PLS_HIP_OK;
 }
+
+// The optional outputs of a host-memory call, each staged in a device buffer of the handle: out() per output, in the order
+// the copies back are to be issued, then copy_back() behind the work.  (Contiguous fp64 matrices: rows x cols with ld rows.)
+struct HostOutputs {
+    pls_hip_context *c;
+    struct Copy {
+        double *host;
+        const double *dev;
+        i64 rows, cols;
+    };
+    static constexpr int MAX_OUTPUTS = 8;
+    Copy copies[MAX_OUTPUTS];
+    int n = 0;
+    explicit HostOutputs(pls_hip_context *ctx) : c(ctx) {}
+    // dev = where the kernels write `host`'s output (null: not asked for): `off` doubles into `buf` of `total` doubles --
+    // several outputs may share a buffer, each naming its whole size
+    int out(double *&dev, double *host, DevBuf &buf, i64 total, i64 off, i64 rows, i64 cols) {
+        dev = nullptr;
+        if (!host) return PLS_HIP_OK;
+        if (n == MAX_OUTPUTS) return fail(c, PLS_HIP_ERR_INVALID, "internal: more staged outputs than HostOutputs holds");
+        CHK(ensure(c, buf, (size_t)total * 8));
+        dev = (double *)buf.p + off;
+        copies[n++] = {host, dev, rows, cols};
+        return PLS_HIP_OK;
+    }
+    int copy_back() {
+        for (int i = 0; i < n; ++i) {
+            const Copy &o = copies[i];
+            CHK(d2h(c, o.host, o.rows, o.dev, o.rows, o.rows, o.cols, 8));
+        }
+        return PLS_HIP_OK;
+    }
+};
 
 // Upload of X (host, rows x K) in ROW blocks with X^T X and X^T Y accumulated block by block on the compute stream
 // while the DMA engine already moves the next block: the matrix-core SYRK of a block (2 rb K^2 flops) takes a

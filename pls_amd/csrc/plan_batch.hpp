@@ -186,64 +186,49 @@ int fit_batch_impl(pls_hip_context *h, const void *X, i64 ldx, const void *Ys, i
     const void *dX = X, *dY = Ys;
     i64 dldx = ldx, dldy = ldy;
     double *dR = R, *dQ = Q, *dtt = tt, *dB = B, *dssy = ssy;
+    HostOutputs outs(h);
     if (mem == PLS_HIP_MEM_HOST) {
         const i64 n1 = std::max<i64>(N, 1), ldn = n1 + ((-n1) & 3);  // 16-byte columns for either type
         CHK(ensure(h, h->hX, (size_t)ldn * K * es));
         CHK(ensure(h, h->bY, (size_t)ldn * C * es));
-        if (R) CHK(ensure(h, h->boR, (size_t)nprob * K * A * 8));
-        if (Q) CHK(ensure(h, h->boQ, (size_t)nprob * M * A * 8));
-        if (tt) CHK(ensure(h, h->bott, (size_t)nprob * A * 8));
-        if (B) CHK(ensure(h, h->boB, (size_t)nprob * K * M * 8));
-        if (ssy) CHK(ensure(h, h->bossy, (size_t)nprob * M * 8));
+        CHK(outs.out(dR, R, h->boR, nprob * K * A, 0, K * A, nprob));
+        CHK(outs.out(dQ, Q, h->boQ, nprob * M * A, 0, M * A, nprob));
+        CHK(outs.out(dtt, tt, h->bott, nprob * A, 0, A, nprob));
+        CHK(outs.out(dB, B, h->boB, nprob * K * M, 0, K * M, nprob));
+        CHK(outs.out(dssy, ssy, h->bossy, nprob * M, 0, M, nprob));
         CHK(h2d(h, h->hX.p, ldn, X, ldx, N, K, es));
         CHK(h2d(h, h->bY.p, ldn, Ys, ldy, N, C, es));
         dX = h->hX.p; dY = h->bY.p;
         dldx = dldy = ldn;
-        dR = R ? (double *)h->boR.p : nullptr;
-        dQ = Q ? (double *)h->boQ.p : nullptr;
-        dtt = tt ? (double *)h->bott.p : nullptr;
-        dB = B ? (double *)h->boB.p : nullptr;
-        dssy = ssy ? (double *)h->bossy.p : nullptr;
     }
     int rc = PLS_HIP_ERR_ALLOC;
     if (batch_dual_covers(h, N, M)) {  // the sample-space plan, an explicit opt-in: every problem from one X X^T
-        if (dtype == PLS_HIP_F64)
-            rc = fit_batch_dual<double>(h, (const double *)dX, dldx, (const double *)dY, dldy, (int)N, K, (int)M, (int)A, nprob, dR, dQ,
-                                        dtt, dB, dssy);
-        else
-            rc = fit_batch_dual<float>(h, (const float *)dX, dldx, (const float *)dY, dldy, (int)N, K, (int)M, (int)A, nprob, dR, dQ,
-                                       dtt, dB, dssy);
+        rc = by_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
+            return fit_batch_dual<T>(h, (const T *)dX, dldx, (const T *)dY, dldy, (int)N, K, (int)M, (int)A, nprob, dR, dQ, dtt, dB, dssy);
+        });
         if (rc == PLS_HIP_ERR_ALLOC) h->err.clear();  // its workspace does not fit: the routes below
     }
     const bool dual = rc != PLS_HIP_ERR_ALLOC;  // (the sample-space route took the call)
     const bool batched = !dual && batch_covers(h, K, M, A);
-    if (batched) {
-        if (dtype == PLS_HIP_F64)
-            rc = fit_batch_device<double>(h, (const double *)dX, dldx, (const double *)dY, dldy, N, (int)K, (int)M, (int)A, nprob, dR,
-                                          dQ, dtt, dB, dssy);
-        else
-            rc = fit_batch_device<float>(h, (const float *)dX, dldx, (const float *)dY, dldy, N, (int)K, (int)M, (int)A, nprob, dR, dQ,
-                                         dtt, dB, dssy);
-    }
+    if (batched)
+        rc = by_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
+            return fit_batch_device<T>(h, (const T *)dX, dldx, (const T *)dY, dldy, N, (int)K, (int)M, (int)A, nprob, dR, dQ, dtt, dB, dssy);
+        });
     // declined, or (single rank: the ranks of a sharded handle must not differ in their route) no room for the batched workspace
     if (!dual && (!batched || (rc == PLS_HIP_ERR_ALLOC && !h->reducer))) {
         h->err.clear();
         if (M > plsk::LM_MAX || K > 32768)
             return fail(h, PLS_HIP_ERR_UNSUPPORTED, "fit_batch: the per-problem route is pls_hip_fit's: M <= 1024, K <= 32768");
-        if (dtype == PLS_HIP_F64)
-            rc = fit_batch_refit<double>(h, (const double *)dX, dldx, (const double *)dY, dldy, N, (int)K, (int)M, (int)A, nprob, dR, dQ,
-                                         dtt, dB, dssy);
-        else
-            rc = fit_batch_refit<float>(h, (const float *)dX, dldx, (const float *)dY, dldy, N, (int)K, (int)M, (int)A, nprob, dR, dQ,
-                                        dtt, dB, dssy);
+        rc = by_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
+            return fit_batch_refit<T>(h, (const T *)dX, dldx, (const T *)dY, dldy, N, (int)K, (int)M, (int)A, nprob, dR, dQ, dtt, dB, dssy);
+        });
     }
     if (rc != PLS_HIP_OK) return rc;
     if (mem == PLS_HIP_MEM_HOST) {
-        if (R) CHK(d2h(h, R, K * A, dR, K * A, K * A, nprob, 8));
-        if (Q) CHK(d2h(h, Q, M * A, dQ, M * A, M * A, nprob, 8));
-        if (tt) CHK(d2h(h, tt, A, dtt, A, A, nprob, 8));
-        if (B) CHK(d2h(h, B, K * M, dB, K * M, K * M, nprob, 8));
-        if (ssy) CHK(d2h(h, ssy, M, dssy, M, M, nprob, 8));
+        CHK(outs.copy_back());
         HIPCHK(h, hipStreamSynchronize(h->stream));
         CHK(check_diverged(h));
     }

@@ -133,6 +133,14 @@ auto pick_int(int v, F &&f) -> decltype(f(std::integral_constant<int, C0>{})) {
 template <typename F>
 auto with_mm(int M, F &&f) { return pick_int<2, 4, 8>(M, f); }
 
+// f(T{}) with T = double or float as `dtype` (PLS_HIP_F64 / PLS_HIP_F32) says: the run-time choice between the two
+// instantiations of a plan.  In f: `[&](auto t) { using T = decltype(t); ... }`.
+template <typename F>
+auto by_dtype(int dtype, F &&f) -> decltype(f(double{})) {
+    if (dtype == PLS_HIP_F64) return f(double{});
+    return f(float{});
+}
+
 // Items (problems, folds) per round of a call that works through n of them with per_item_bytes of workspace each: as many as
 // 4 GB and half of the free device memory hold, at most value_cap (index ranges) and env_cap (> 0: the test knob).  0: not even one.
 constexpr i64 ROUND_BYTES = (i64)4 << 30;

@@ -363,22 +363,14 @@ int cv_folds_sharded(pls_hip_context *h, const void *X, i64 ldx, const void *Y, 
     double *dE = (mem == PLS_HIP_MEM_HOST) ? (double *)h->cve.p : E;
     HIPCHK(h, hipMemcpyAsync(h->cvidx.p, test_idx, (size_t)nobs * 8, hipMemcpyHostToDevice, h->stream));
     const int Ki = (int)K, Mi = (int)M, Ai = (int)A, tsi = (int)ts;
-    int rc;
-    if (batched) {
-        if (dtype == PLS_HIP_F64)
-            rc = cv_folds_sharded_batched<double>(h, (const double *)dX, dldx, (const double *)dY, dldy, N, row0, Ki, Mi, Ai, tsi,
-                                                  num_folds, fold0, nfold, fchunk, dE);
-        else
-            rc = cv_folds_sharded_batched<float>(h, (const float *)dX, dldx, (const float *)dY, dldy, N, row0, Ki, Mi, Ai, tsi,
-                                                 num_folds, fold0, nfold, fchunk, dE);
-    } else {
-        if (dtype == PLS_HIP_F64)
-            rc = cv_folds_sharded_refit<double>(h, (const double *)dX, dldx, (const double *)dY, dldy, N, row0, Ki, Mi, Ai,
-                                                test_idx, tsi, num_folds, fchunk, dE);
-        else
-            rc = cv_folds_sharded_refit<float>(h, (const float *)dX, dldx, (const float *)dY, dldy, N, row0, Ki, Mi, Ai,
-                                               test_idx, tsi, num_folds, fchunk, dE);
-    }
+    const int rc = by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        if (batched)
+            return cv_folds_sharded_batched<T>(h, (const T *)dX, dldx, (const T *)dY, dldy, N, row0, Ki, Mi, Ai, tsi, num_folds, fold0, nfold,
+                                               fchunk, dE);
+        return cv_folds_sharded_refit<T>(h, (const T *)dX, dldx, (const T *)dY, dldy, N, row0, Ki, Mi, Ai, test_idx, tsi, num_folds, fchunk,
+                                         dE);
+    });
     if (rc != PLS_HIP_OK) return rc;
     if (mem == PLS_HIP_MEM_HOST)
         HIPCHK(h, hipMemcpyAsync(E, dE, (size_t)nobs * A * M * 8, hipMemcpyDeviceToHost, h->stream));

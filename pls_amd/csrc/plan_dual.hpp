@@ -19,7 +19,12 @@ inline const char *dual_refusal(const pls_hip_context *c, i64 N, i64 M) {
     return nullptr;
 }
 
-// The sweep over X that both users of the plan begin with (the fit, the cross-validation folds of plan_dual_cv.hpp):
+// what every multi-item route of the plan (dual_round.hpp) asks of a call, besides its own *_REFIT switch and lower bound on N
+inline bool dual_rounds_cover(const pls_hip_context *c, i64 N, i64 M) {
+    return c->opt_algo == PLS_HIP_ALGO_DUAL && !c->reducer && c->nranks == 1 && N <= plsk::DUAL_NMAX && M <= plsk::DUAL_MMAX;
+}
+
+// The sweep over X that every user of the plan begins with (the fit here, the rounds of dual_round.hpp):
 // c->dG = G = X X^T on the matrix cores, one bracket of PLS_HIP_FAM_XTY.
 template <typename T>
 int dual_gram(pls_hip_context *c, const T *X, i64 ldx, int N, int K) {

@@ -2,7 +2,7 @@
 // jack-knife, a case-weighted fit), the coefficients of every replicate and their summaries about the unit-weight fit.
 // Part of libpls_hip.so: included by pls_hip.hip (one translation unit), in the order given there.
 //
-// Sample-space route (fit_resampled_dual, under PLS_HIP_ALGO_DUAL): G = X X^T once, the replicates in rounds; per component a
+// Sample-space route (fit_resampled_dual, under PLS_HIP_ALGO_DUAL): G = X X^T once, the replicates in rounds (DualRounds, dual_round.hpp); per component a
 // round costs one product Z = G [s o Y~_a of every replicate] and one launch of resample_step_kernel, a workgroup per
 // replicate (resample_kernels.hpp has the algebra).  B of a round is one product X^T [s o D(0) | s o D(1) | ...].  The
 // unit-weight fit behind B0 and the summaries is replicate "-1": it leads the first round and takes every kernel a replicate
@@ -14,12 +14,8 @@ namespace {
 
 // the calls the sample-space route takes (the conditions of batch_dual_covers); every other call takes the general route
 bool resample_dual_covers(const pls_hip_context *c, i64 N, i64 M) {
-    return c->opt_algo == PLS_HIP_ALGO_DUAL && !c->reducer && c->nranks == 1 && N >= 1 && N <= plsk::DUAL_NMAX &&
-           M <= plsk::DUAL_MMAX && !c->env.resample_refit;
+    return N >= 1 && dual_rounds_cover(c, N, M) && !c->env.resample_refit;
 }
-
-// doubles of one replicate's state: that of a fit_batch problem, s (N) and the product's input s o Y~_a (N x M)
-i64 resample_item_doubles(i64 N, i64 M, i64 A) { return batch_dual_problem_doubles(N, M, A) + N + N * M; }
 
 // s1, s2 and (B0 not asked for) the unit-weight coefficients: c->rsacc, 3 K M doubles
 int resample_accumulators(pls_hip_context *c, i64 KM, bool summary, double *B0, double *&s1, double *&s2, double *&B0d) {
@@ -54,60 +50,59 @@ int resample_finish(pls_hip_context *c, const double *B0d, const double *s1, con
 template <typename T>
 int fit_resampled_dual(pls_hip_context *c, const T *X, i64 ldx, const T *Y, i64 ldy, int N, i64 K, int M, int A, const double *Wt,
                        i64 ldw, i64 nrep, double *Q, double *tt, double *B, double *B0, double *Bmean, double *Bm2) {
-    const i64 NN = (i64)N * N, NM = (i64)N * M, NA = (i64)N * A, KM = K * M, MA = (i64)M * A, es = (i64)sizeof(T);
+    const i64 NM = (i64)N * M, NA = (i64)N * A, KM = K * M, MA = (i64)M * A, es = (i64)sizeof(T);
     const bool summary = Bmean || Bm2, need0 = B0 || summary;
     const i64 off = need0 ? 1 : 0, items = nrep + off;  // item i is replicate i - off; replicate -1: the unit-weight fit
     if (A > ((i64)1 << 20)) return fail(c, PLS_HIP_ERR_ALLOC, "fit_resampled: the workspace of one replicate does not fit");
-    // G and the partial blocks of its sweep first: the round is sized by what they leave
-    CHK(ensure(c, c->dG, (size_t)NN * 8));
-    CHK(ensure(c, c->dY, (size_t)NM * 8));
+    CHK(ensure(c, c->dY, (size_t)NM * 8));  // before G: the round is sized by what is left
     Range r_call("pls_hip_fit_resampled (sample space)");
-    CHK(dual_gram<T>(c, X, ldx, N, (int)K));  // the only pass over X unless B, B0, Bmean or Bm2 is asked for
-    // (a summary without B: the round's block of B is workspace)
-    const i64 per = (resample_item_doubles(N, M, A) + (summary && !B ? KM : 0)) * 8;
-    const i64 nround = round_size(per, ((i64)1 << 30) / ((i64)N * std::max(M, A)), c->env.resample_round, items);
-    if (nround < 1) return fail(c, PLS_HIP_ERR_ALLOC, "fit_resampled: the workspace of one replicate does not fit");
-    CHK(ensure(c, c->rsw, (size_t)(nround * resample_item_doubles(N, M, A) * 8)));
-    if (summary && !B) CHK(ensure(c, c->rsB, (size_t)(nround * KM * 8)));
+    DualRounds r;
+    // (the only pass over X unless B, B0, Bmean or Bm2 is asked for.)  A summary without B: the round's block of B is
+    // workspace, K M doubles per replicate beside the slab
+    DualRounds::Sizing sz;
+    sz.items = items;
+    sz.extra_bytes = summary && !B ? KM * 8 : 0;
+    sz.value_cap = ((i64)1 << 30) / ((i64)N * std::max(M, A));
+    sz.env_cap = c->env.resample_round;
+    sz.refusal = "fit_resampled: the workspace of one replicate does not fit";
+    CHK(r.open<T>(c, X, ldx, N, (int)K, M, plsk::resample_layout(N, M, A), sz, c->rsw));
+    if (summary && !B) CHK(ensure(c, c->rsB, (size_t)(r.nround * KM * 8)));
     double *s1 = nullptr, *s2 = nullptr, *B0d = nullptr;
     if (need0) CHK(resample_accumulators(c, KM, summary, B0, s1, s2, B0d));
-    const double *G = (const double *)c->dG.p;
     double *Y64 = (double *)c->dY.p;
-    double *Ya = (double *)c->rsw.p, *Z = Ya + nround * NM, *T64 = Z + nround * NM, *U = T64 + nround * NA, *C = U + nround * NA;
-    double *Qw = C + nround * A * A, *ttw = Qw + nround * MA, *scr = ttw + nround * A, *sv = scr + nround * (N + A);
-    double *Yin = sv + nround * N;
-    // one product kernel and one back-projection kernel for the whole call, as the other two routes choose theirs: the bits of
-    // a replicate do not depend on the round it falls into
-    const bool gy = nround * M <= 32, blocks = nround * M > plsk::XTV_NC;
+    double *Ya = r.field(plsk::DUAL_YA), *Z = r.field(plsk::DUAL_Z), *T64 = r.field(plsk::BAT_T), *U = r.field(plsk::BAT_U);
+    double *C = r.field(plsk::BAT_C), *Qw = r.field(plsk::BAT_Q), *ttw = r.field(plsk::BAT_TT), *scr = r.field(plsk::BAT_SCR);
+    double *sv = r.field(plsk::RS_S), *Yin = r.field(plsk::RS_YIN);
+    // one back-projection kernel for the whole call, as the product has one (dual_round.hpp): the bits of a replicate do not
+    // depend on the round it falls into
+    const bool blocks = r.nround * M > plsk::XTV_NC;
     {
         Scope s(c, PLS_HIP_FAM_SMALL, NM * (es + 8));
         hipLaunchKernelGGL((plsk::dual_convert_kernel<T, double>), dim3((unsigned)((NM + 255) / 256)), dim3(256), 0, c->stream, Y, ldy,
                            Y64, (i64)N, N, M);
         LAUNCH_CHECK(c);
     }
-    for (i64 i0 = 0; i0 < items; i0 += nround) {
-        Range r_round("round of replicates", (int)(i0 / nround));
-        const i64 nb = std::min(nround, items - i0), rep0 = i0 - off;
+    auto init = [&](i64 i0, i64 nb) -> int {
+        Scope s(c, PLS_HIP_FAM_SMALL, nb * (3 * NM + 2 * (i64)N) * 8);
+        hipLaunchKernelGGL(plsk::resample_init_kernel, dim3((unsigned)nb), dim3(plsk::WG), 0, c->stream, Wt, ldw, i0 - off,
+                           (const double *)Y64, N, M, sv, Ya, Yin);
+        LAUNCH_CHECK(c);
+        return PLS_HIP_OK;
+    };
+    auto step = [&](i64, i64 nb, int a) -> int {
+        Scope s(c, PLS_HIP_FAM_SMALL, nb * (i64)N * (4 * M + a + 5) * 8);
+        hipLaunchKernelGGL(plsk::resample_step_kernel, dim3((unsigned)nb), dim3(plsk::UPD_THREADS), 0, c->stream, (const double *)Z, Ya,
+                           T64, U, Qw, C, ttw, scr, (const double *)sv, Yin, N, M, A, a, (int)c->opt_power_iters);
+        LAUNCH_CHECK(c);
+        return PLS_HIP_OK;
+    };
+    auto after = [&](i64 i0, i64 nb) -> int {
+        const i64 rep0 = i0 - off;
         const i64 lead = rep0 < 0 ? 1 : 0, nr = nb - lead, r0 = rep0 + lead;  // the unit-weight fit leads the first round
-        const int Cy = (int)(nb * M);
-        {
-            Scope s(c, PLS_HIP_FAM_SMALL, nb * (3 * NM + 2 * (i64)N) * 8);
-            hipLaunchKernelGGL(plsk::resample_init_kernel, dim3((unsigned)nb), dim3(plsk::WG), 0, c->stream, Wt, ldw, rep0,
-                               (const double *)Y64, N, M, sv, Ya, Yin);
-            LAUNCH_CHECK(c);
-        }
-        for (int a = 0; a < A; ++a) {
-            if (gy) CHK(launch_dual_gy(c, G, Yin, N, Cy, Z));
-            else CHK(launch_sym_product(c, G, N, Yin, (i64)N, Cy, Z, (i64)N));
-            Scope s(c, PLS_HIP_FAM_SMALL, nb * (i64)N * (4 * M + a + 5) * 8);
-            hipLaunchKernelGGL(plsk::resample_step_kernel, dim3((unsigned)nb), dim3(plsk::UPD_THREADS), 0, c->stream, (const double *)Z,
-                               Ya, T64, U, Qw, C, ttw, scr, (const double *)sv, Yin, N, M, A, a, (int)c->opt_power_iters);
-            LAUNCH_CHECK(c);
-        }
         if (Q && nr > 0) HIPCHK(c, hipMemcpyAsync(Q + r0 * MA, Qw + lead * MA, (size_t)(nr * MA * 8), hipMemcpyDeviceToDevice, c->stream));
         if (tt && nr > 0) HIPCHK(c, hipMemcpyAsync(tt + r0 * A, ttw + lead * A, (size_t)(nr * A * 8), hipMemcpyDeviceToDevice, c->stream));
         const bool back = nr > 0 && (B || summary);  // the replicates' coefficients are wanted
-        if (!lead && !back) continue;
+        if (!lead && !back) return PLS_HIP_OK;
         {
             Scope s(c, PLS_HIP_FAM_SMALL, nb * (2 * NA + (i64)A * A + MA + NM + N) * 8);
             hipLaunchKernelGGL(plsk::resample_sd_kernel, dim3((unsigned)nb), dim3(plsk::WG), 0, c->stream, U, (const double *)C,
@@ -116,11 +111,13 @@ int fit_resampled_dual(pls_hip_context *c, const T *X, i64 ldx, const T *Y, i64 
         }
         Range r_b("X^T [s o D]");
         if (lead) CHK(batch_dual_xtv<T>(c, X, ldx, N, K, Z, M, B0d, blocks));
-        if (!back) continue;
+        if (!back) return PLS_HIP_OK;
         double *Br = B ? B + r0 * KM : (double *)c->rsB.p;
         CHK(batch_dual_xtv<T>(c, X, ldx, N, K, Z + lead * NM, (int)(nr * M), Br, blocks));
         if (summary) CHK(resample_accumulate(c, Br, B0d, KM, nr, s1, s2));
-    }
+        return PLS_HIP_OK;
+    };
+    CHK(r.run(c, N, M, A, plsk::RS_YIN, "round of replicates", init, step, after));
     if (summary) CHK(resample_finish(c, B0d, s1, s2, KM, nrep, Bmean, Bm2));
     return PLS_HIP_OK;
 }
@@ -180,54 +177,43 @@ int fit_resampled_impl(pls_hip_context *h, const void *X, i64 ldx, const void *Y
     const double *dW = Wt;
     i64 dldx = ldx, dldy = ldy, dldw = ldw;
     double *dQ = Q, *dtt = tt, *dB = B, *dB0 = B0, *dBmean = Bmean, *dBm2 = Bm2;
+    HostOutputs outs(h);
     if (mem == PLS_HIP_MEM_HOST) {
         const i64 ldn = N + ((-N) & 3);  // 16-byte columns for either type
         CHK(ensure(h, h->hX, (size_t)ldn * K * es));
         CHK(ensure(h, h->hY, (size_t)ldn * M * es));
         CHK(ensure(h, h->rsW, (size_t)N * nrep * 8));
-        if (Q) CHK(ensure(h, h->boQ, (size_t)nrep * M * A * 8));
-        if (tt) CHK(ensure(h, h->bott, (size_t)nrep * A * 8));
-        if (B) CHK(ensure(h, h->boB, (size_t)nrep * KM * 8));
-        if (B0 || Bmean || Bm2) CHK(ensure(h, h->rsoS, (size_t)3 * KM * 8));
+        CHK(outs.out(dQ, Q, h->boQ, nrep * M * A, 0, M * A, nrep));
+        CHK(outs.out(dtt, tt, h->bott, nrep * A, 0, A, nrep));
+        CHK(outs.out(dB, B, h->boB, nrep * KM, 0, KM, nrep));
+        CHK(outs.out(dB0, B0, h->rsoS, 3 * KM, 0, KM, 1));  // rsoS = [B0 | Bmean | Bm2]
+        CHK(outs.out(dBmean, Bmean, h->rsoS, 3 * KM, KM, KM, 1));
+        CHK(outs.out(dBm2, Bm2, h->rsoS, 3 * KM, 2 * KM, KM, 1));
         CHK(h2d(h, h->hX.p, ldn, X, ldx, N, K, es));
         CHK(h2d(h, h->hY.p, ldn, Y, ldy, N, M, es));
         CHK(h2d(h, h->rsW.p, N, Wt, ldw, N, nrep, 8));
         dX = h->hX.p; dY = h->hY.p; dW = (const double *)h->rsW.p;
         dldx = dldy = ldn;
         dldw = N;
-        dQ = Q ? (double *)h->boQ.p : nullptr;
-        dtt = tt ? (double *)h->bott.p : nullptr;
-        dB = B ? (double *)h->boB.p : nullptr;
-        dB0 = B0 ? (double *)h->rsoS.p : nullptr;
-        dBmean = Bmean ? (double *)h->rsoS.p + KM : nullptr;
-        dBm2 = Bm2 ? (double *)h->rsoS.p + 2 * KM : nullptr;
     }
     int rc = PLS_HIP_ERR_ALLOC;
     if (resample_dual_covers(h, N, M)) {  // the sample-space plan, an explicit opt-in: every replicate from one X X^T
-        if (dtype == PLS_HIP_F64)
-            rc = fit_resampled_dual<double>(h, (const double *)dX, dldx, (const double *)dY, dldy, (int)N, K, (int)M, (int)A, dW, dldw,
-                                            nrep, dQ, dtt, dB, dB0, dBmean, dBm2);
-        else
-            rc = fit_resampled_dual<float>(h, (const float *)dX, dldx, (const float *)dY, dldy, (int)N, K, (int)M, (int)A, dW, dldw,
-                                           nrep, dQ, dtt, dB, dB0, dBmean, dBm2);
+        rc = by_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
+            return fit_resampled_dual<T>(h, (const T *)dX, dldx, (const T *)dY, dldy, (int)N, K, (int)M, (int)A, dW, dldw, nrep, dQ, dtt,
+                                         dB, dB0, dBmean, dBm2);
+        });
         if (rc == PLS_HIP_ERR_ALLOC) h->err.clear();  // its workspace does not fit: the general route
     }
-    if (rc == PLS_HIP_ERR_ALLOC) {
-        if (dtype == PLS_HIP_F64)
-            rc = fit_resampled_refit<double>(h, (const double *)dX, dldx, (const double *)dY, dldy, N, (int)K, (int)M, (int)A, dW, dldw,
-                                             nrep, dQ, dtt, dB, dB0, dBmean, dBm2);
-        else
-            rc = fit_resampled_refit<float>(h, (const float *)dX, dldx, (const float *)dY, dldy, N, (int)K, (int)M, (int)A, dW, dldw,
-                                            nrep, dQ, dtt, dB, dB0, dBmean, dBm2);
-    }
+    if (rc == PLS_HIP_ERR_ALLOC)
+        rc = by_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
+            return fit_resampled_refit<T>(h, (const T *)dX, dldx, (const T *)dY, dldy, N, (int)K, (int)M, (int)A, dW, dldw, nrep, dQ, dtt,
+                                          dB, dB0, dBmean, dBm2);
+        });
     if (rc != PLS_HIP_OK) return rc;
     if (mem == PLS_HIP_MEM_HOST) {
-        if (Q) CHK(d2h(h, Q, M * A, dQ, M * A, M * A, nrep, 8));
-        if (tt) CHK(d2h(h, tt, A, dtt, A, A, nrep, 8));
-        if (B) CHK(d2h(h, B, KM, dB, KM, KM, nrep, 8));
-        if (B0) CHK(d2h(h, B0, KM, dB0, KM, KM, 1, 8));
-        if (Bmean) CHK(d2h(h, Bmean, KM, dBmean, KM, KM, 1, 8));
-        if (Bm2) CHK(d2h(h, Bm2, KM, dBm2, KM, KM, 1, 8));
+        CHK(outs.copy_back());
         HIPCHK(h, hipStreamSynchronize(h->stream));
         CHK(check_diverged(h));
     }

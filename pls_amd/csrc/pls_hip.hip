@@ -324,12 +324,11 @@ int pls_hip_fit(pls_hip_handle h, const void *X, int64_t ldx, const void *Y, int
                                     plsk::micro_fit_covers(N, Ki, Mi, Ai, ldn, es));  // (no use for X^T X there)
         if (wants_gram && !single_launch && !h->reducer && N > 0 && K <= 4096 && ensure(h, h->gxx, (size_t)K * K * 8) == PLS_HIP_OK &&
             ensure(h, h->gxy, (size_t)K * M * 8) == PLS_HIP_OK) {
-            if (dtype == PLS_HIP_F64)
-                CHK(upload_accumulate<double>(h, (double *)h->hX.p, ldn, (const double *)X, ldx, N, Ki, (const double *)h->hY.p, ldn,
-                                              Mi, (double *)h->gxx.p, (double *)h->gxy.p, &pre));
-            else
-                CHK(upload_accumulate<float>(h, (float *)h->hX.p, ldn, (const float *)X, ldx, N, Ki, (const float *)h->hY.p, ldn, Mi,
-                                             (double *)h->gxx.p, (double *)h->gxy.p, &pre));
+            CHK(by_dtype(dtype, [&](auto t) {
+                using Tx = decltype(t);
+                return upload_accumulate<Tx>(h, (Tx *)h->hX.p, ldn, (const Tx *)X, ldx, N, Ki, (const Tx *)h->hY.p, ldn, Mi, (double *)h->gxx.p,
+                                            (double *)h->gxy.p, &pre);
+            }));
         } else {
             h->err.clear();
             CHK(h2d(h, h->hX.p, ldn, X, ldx, N, K, es));
@@ -368,13 +367,10 @@ int pls_hip_fit(pls_hip_handle h, const void *X, int64_t ldx, const void *Y, int
         HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
     }
     begin_fit_timing(h);
-    int rc;
-    if (dtype == PLS_HIP_F64)
-        rc = fit_device<double>(h, (const double *)dX, dldx, (const double *)dY, dldy, N, Ki, Mi, Ai, method,
-                                dW, dP, dQ, dR, (double *)dT, dldt, dB);
-    else
-        rc = fit_device<float>(h, (const float *)dX, dldx, (const float *)dY, dldy, N, Ki, Mi, Ai, method, dW,
-                               dP, dQ, dR, (float *)dT, dldt, dB);
+    const int rc = by_dtype(dtype, [&](auto t) {
+        using Tx = decltype(t);
+        return fit_device<Tx>(h, (const Tx *)dX, dldx, (const Tx *)dY, dldy, N, Ki, Mi, Ai, method, dW, dP, dQ, dR, (Tx *)dT, dldt, dB);
+    });
     end_fit_timing(h);
     if (capture) {
         hipGraph_t graph = nullptr;
@@ -465,10 +461,10 @@ int pls_hip_xb(pls_hip_handle h, const void *X, int64_t ldx, int64_t N, int64_t 
         return fail(h, PLS_HIP_ERR_INVALID, "bad mem kind");
     }
     int nss = 0;
-    if (dtype == PLS_HIP_F64)
-        CHK(launch_xb<double>(h, (const double *)dX, dldx, N, (int)K, dBm, dldb, (int)C, (double *)dO, dldo, nullptr, &nss));
-    else
-        CHK(launch_xb<float>(h, (const float *)dX, dldx, N, (int)K, dBm, dldb, (int)C, (float *)dO, dldo, nullptr, &nss));
+    CHK(by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_xb<T>(h, (const T *)dX, dldx, N, (int)K, dBm, dldb, (int)C, (T *)dO, dldo, nullptr, &nss);
+    }));
     if (mem == PLS_HIP_MEM_HOST) {
         CHK(d2h(h, out, ldo, dO, dldo, N, C, es));
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -485,10 +481,10 @@ int pls_hip_xty(pls_hip_handle h, const void *X, int64_t ldx, const void *Y, int
     CHK(set_device(h));
     CHK(ensure(h, h->part, (size_t)max_partial_rows(h, N, (int)K) * (size_t)(K * M) * 8));
     int nb = 0;
-    if (dtype == PLS_HIP_F64)
-        CHK(launch_xty<double>(h, (const double *)X, ldx, (const double *)Y, ldy, N, (int)K, (int)M, (double *)h->part.p, &nb));
-    else
-        CHK(launch_xty<float>(h, (const float *)X, ldx, (const float *)Y, ldy, N, (int)K, (int)M, (double *)h->part.p, &nb));
+    CHK(by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_xty<T>(h, (const T *)X, ldx, (const T *)Y, ldy, N, (int)K, (int)M, (double *)h->part.p, &nb);
+    }));
     CHK(ensure(h, h->red, (size_t)plsk::RED_SLICES * (size_t)(K * M) * 8));
     CHK(launch_reduce(h, (const double *)h->part.p, nb, (int)(K * M), nullptr, 0, (double *)h->red.p));
     const int nblk = (int)((K * M + plsk::WG - 1) / plsk::WG);
@@ -505,9 +501,10 @@ int pls_hip_deflate(pls_hip_handle h, const void *src, int64_t lds, void *dst, i
     if (N < 1 || K < 1 || K > (1 << 30) || !src || !dst || !t || !p || lds < N || ldd < N)
         return fail(h, PLS_HIP_ERR_INVALID, "bad deflate arguments");
     CHK(set_device(h));
-    if (dtype == PLS_HIP_F64)
-        return launch_deflate<double>(h, (const double *)src, lds, (double *)dst, ldd, N, (int)K, (const double *)t, p);
-    return launch_deflate<float>(h, (const float *)src, lds, (float *)dst, ldd, N, (int)K, (const float *)t, p);
+    return by_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        return launch_deflate<T>(h, (const T *)src, lds, (T *)dst, ldd, N, (int)K, (const T *)t, p);
+    });
 }
 
 }  // extern "C"
@@ -525,9 +522,10 @@ int pls_hip_colwise_z_scores(pls_hip_handle h, const void *X, int64_t ldx, int64
         ldx < std::max<i64>(N, 1) || (Z && ldz < std::max<i64>(N, 1)))
         return fail(h, PLS_HIP_ERR_INVALID, "bad z-score arguments");
     CHK(set_device(h));
-    if (dtype == PLS_HIP_F64)
-        return zscores_device<double>(h, (const double *)X, ldx, N, n_total, (int)K, (double *)Z, ldz, mean, sd);
-    return zscores_device<float>(h, (const float *)X, ldx, N, n_total, (int)K, (float *)Z, ldz, mean, sd);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return zscores_device<T>(h, (const T *)X, ldx, N, n_total, (int)K, (T *)Z, ldz, mean, sd);
+    });
 }
 
 int pls_hip_sse_by_components(pls_hip_handle h, const void *S, int64_t lds, const void *Y, int64_t ldy,
@@ -537,14 +535,16 @@ int pls_hip_sse_by_components(pls_hip_handle h, const void *S, int64_t lds, cons
     if (N < 1 || A < 1 || M < 1 || M > 1024 || A > (1 << 20) || !S || !Y || !Q || !SSE || lds < N || ldy < N)
         return fail(h, PLS_HIP_ERR_INVALID, "bad sse arguments");
     CHK(set_device(h));
-    if (dtype == PLS_HIP_F64)
-        return sse_device<double>(h, (const double *)S, lds, (const double *)Y, ldy, N, (int)A, (int)M, Q, SSE);
-    return sse_device<float>(h, (const float *)S, lds, (const float *)Y, ldy, N, (int)A, (int)M, Q, SSE);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return sse_device<T>(h, (const T *)S, lds, (const T *)Y, ldy, N, (int)A, (int)M, Q, SSE);
+    });
 }
 
 }  // extern "C"
 
 #include "plan_cv.hpp"
+#include "dual_round.hpp"
 #include "plan_dual_cv.hpp"
 #include "plan_dual_batch.hpp"
 #include "plan_batch.hpp"
@@ -597,40 +597,36 @@ int pls_hip_cv_folds(pls_hip_handle h, const void *X, int64_t ldx, const void *Y
     const bool tiny_m = plsk::tiny_fit_m_covers(N, (int)K, (int)M, (int)A, dldx, es) && !h->env.cv_refit && h->env.tiny;
     const bool micro = plsk::micro_fit_covers(N, (int)K, (int)M, (int)A, dldx, es) && !h->env.cv_refit && h->env.tiny;
     if (cv_dual_covers(h, N, M)) {  // the sample-space plan, an explicit opt-in: every fold from one X X^T
-        if (dtype == PLS_HIP_F64)
-            rc = cv_folds_dual<double>(h, (const double *)dX, dldx, (const double *)dY, dldy, (int)N, (int)K, (int)M, (int)A, test_idx,
-                                       (int)test_size, num_folds, dE);
-        else
-            rc = cv_folds_dual<float>(h, (const float *)dX, dldx, (const float *)dY, dldy, (int)N, (int)K, (int)M, (int)A, test_idx,
-                                      (int)test_size, num_folds, dE);
+        rc = by_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
+            return cv_folds_dual<T>(h, (const T *)dX, dldx, (const T *)dY, dldy, (int)N, (int)K, (int)M, (int)A, test_idx, (int)test_size,
+                                    num_folds, dE);
+        });
         if (rc == PLS_HIP_ERR_ALLOC) h->err.clear();  // its workspace does not fit: the routes below
     }
     if (rc != PLS_HIP_ERR_ALLOC) {
         // (the sample-space route took the call)
     } else if (micro || tiny || tiny_m) {  // a single-launch fit per fold, in this order of preference
         const FoldKernel kind = micro ? FoldKernel::micro : tiny ? FoldKernel::tiny : FoldKernel::tiny_m;
-        if (dtype == PLS_HIP_F64)
-            rc = cv_folds_single_launch<double>(h, kind, (const double *)dX, dldx, (const double *)dY, dldy, N, (int)K, (int)M, (int)A,
-                                                test_idx, (int)test_size, num_folds, dE);
-        else
-            rc = cv_folds_single_launch<float>(h, kind, (const float *)dX, dldx, (const float *)dY, dldy, N, (int)K, (int)M, (int)A,
-                                               test_idx, (int)test_size, num_folds, dE);
+        rc = by_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
+            return cv_folds_single_launch<T>(h, kind, (const T *)dX, dldx, (const T *)dY, dldy, N, (int)K, (int)M, (int)A, test_idx,
+                                             (int)test_size, num_folds, dE);
+        });
     } else if (cv_batched_covers(h, K, M, A)) {
-        if (dtype == PLS_HIP_F64)
-            rc = cv_folds_device<double>(h, (const double *)dX, dldx, (const double *)dY, dldy, N, (int)K, (int)M, (int)A,
-                                         test_idx, (int)test_size, num_folds, dE);
-        else
-            rc = cv_folds_device<float>(h, (const float *)dX, dldx, (const float *)dY, dldy, N, (int)K, (int)M, (int)A,
-                                        test_idx, (int)test_size, num_folds, dE);
+        rc = by_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
+            return cv_folds_device<T>(h, (const T *)dX, dldx, (const T *)dY, dldy, N, (int)K, (int)M, (int)A, test_idx, (int)test_size,
+                                      num_folds, dE);
+        });
     }
     if (rc == PLS_HIP_ERR_ALLOC) {  // declined, or the per-fold workspaces of the batched form do not fit: one refit per fold
         h->err.clear();
-        if (dtype == PLS_HIP_F64)
-            rc = cv_folds_refit<double>(h, (const double *)dX, dldx, (const double *)dY, dldy, N, (int)K, (int)M, (int)A,
-                                        test_idx, (int)test_size, num_folds, dE);
-        else
-            rc = cv_folds_refit<float>(h, (const float *)dX, dldx, (const float *)dY, dldy, N, (int)K, (int)M, (int)A,
-                                       test_idx, (int)test_size, num_folds, dE);
+        rc = by_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
+            return cv_folds_refit<T>(h, (const T *)dX, dldx, (const T *)dY, dldy, N, (int)K, (int)M, (int)A, test_idx, (int)test_size,
+                                     num_folds, dE);
+        });
     }
     if (rc != PLS_HIP_OK) return rc;
     if (mem == PLS_HIP_MEM_HOST)
@@ -727,15 +723,12 @@ int pls_hip_model_sse(pls_hip_handle h, const void *X, int64_t ldx, const void *
         dldx = dldy = ldn;
     }
     CHK(ensure(h, h->hOut, (size_t)ldn * A * es));  // the scores S = X R stay on the device
-    int nss = 0, rc;
-    if (dtype == PLS_HIP_F64) {
-        if (N > 0) CHK(launch_xb<double>(h, (const double *)dX, dldx, N, (int)K, dR, K, (int)A, (double *)h->hOut.p, ldn, nullptr, &nss));
-        rc = sse_device<double>(h, (const double *)h->hOut.p, ldn, (const double *)dY, dldy, N, (int)A, (int)M, dQ, dE);
-    } else {
-        if (N > 0) CHK(launch_xb<float>(h, (const float *)dX, dldx, N, (int)K, dR, K, (int)A, (float *)h->hOut.p, ldn, nullptr, &nss));
-        rc = sse_device<float>(h, (const float *)h->hOut.p, ldn, (const float *)dY, dldy, N, (int)A, (int)M, dQ, dE);
-    }
-    if (rc != PLS_HIP_OK) return rc;
+    int nss = 0;
+    CHK(by_dtype(dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        if (N > 0) CHK(launch_xb<T>(h, (const T *)dX, dldx, N, (int)K, dR, K, (int)A, (T *)h->hOut.p, ldn, nullptr, &nss));
+        return sse_device<T>(h, (const T *)h->hOut.p, ldn, (const T *)dY, dldy, N, (int)A, (int)M, dQ, dE);
+    }));
     if (mem == PLS_HIP_MEM_HOST) {
         CHK(d2h(h, SSE, M, dE, M, M, A, 8));
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -798,14 +791,11 @@ int pls_hip_x_diagnostics(pls_hip_handle h, const void *X, int64_t ldx, int64_t 
         dsst = sst ? small + 2 * A + 1 : nullptr;
         dldx = dldq = dldt2 = dlds = ldn;
     }
-    int rc;
-    if (dtype == PLS_HIP_F64)
-        rc = xdiag_device<double>(h, (const double *)dX, dldx, N, n_total, (int)K, (int)A, dR, dP, dtv, dQ, dldq, dT2, dldt2,
-                                  (double *)dS, dlds, dssx, dsst);
-    else
-        rc = xdiag_device<float>(h, (const float *)dX, dldx, N, n_total, (int)K, (int)A, dR, dP, dtv, dQ, dldq, dT2, dldt2,
-                                 (float *)dS, dlds, dssx, dsst);
-    if (rc != PLS_HIP_OK) return rc;
+    CHK(by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return xdiag_device<T>(h, (const T *)dX, dldx, N, n_total, (int)K, (int)A, dR, dP, dtv, dQ, dldq, dT2, dldt2, (T *)dS, dlds, dssx,
+                               dsst);
+    }));
     if (mem == PLS_HIP_MEM_HOST) {
         if (Qres) CHK(d2h(h, Qres, ldq, dQ, dldq, N, A, 8));
         if (T2) CHK(d2h(h, T2, ldt2, dT2, dldt2, N, A, 8));
@@ -833,12 +823,11 @@ int pls_hip_synth_x(pls_hip_handle h, void *X, int64_t ldx, int64_t row0, int64_
     LAUNCH_CHECK(h);
     constexpr int KC = 64;
     const dim3 grid((unsigned)((nrows + plsk::WG - 1) / plsk::WG), (unsigned)((K + KC - 1) / KC));
-    if (dtype == PLS_HIP_F64)
-        hipLaunchKernelGGL((plsk::synth_x_kernel<double, KC>), grid, dim3(plsk::WG), 0, h->stream,
-                           (double *)X, ldx, row0, nrows, (int)K, sE, sZ, (const double *)h->tab.p);
-    else
-        hipLaunchKernelGGL((plsk::synth_x_kernel<float, KC>), grid, dim3(plsk::WG), 0, h->stream,
-                           (float *)X, ldx, row0, nrows, (int)K, sE, sZ, (const double *)h->tab.p);
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((plsk::synth_x_kernel<T, KC>), grid, dim3(plsk::WG), 0, h->stream, (T *)X, ldx, row0, nrows, (int)K, sE, sZ,
+                           (const double *)h->tab.p);
+    });
     LAUNCH_CHECK(h);
     return PLS_HIP_OK;
 }
@@ -860,12 +849,11 @@ int pls_hip_synth_y(pls_hip_handle h, void *Y, int64_t ldy, int64_t row0, int64_
                        (double *)h->tab.p, (int)M, sC, 1, (uint64_t)0);
     LAUNCH_CHECK(h);
     const dim3 grid((unsigned)((nrows + plsk::WG - 1) / plsk::WG));
-    if (dtype == PLS_HIP_F64)
-        hipLaunchKernelGGL((plsk::synth_y_kernel<double>), grid, dim3(plsk::WG), 0, h->stream,
-                           (double *)Y, ldy, row0, nrows, (int)M, sZ, sN, (const double *)h->tab.p);
-    else
-        hipLaunchKernelGGL((plsk::synth_y_kernel<float>), grid, dim3(plsk::WG), 0, h->stream, (float *)Y,
-                           ldy, row0, nrows, (int)M, sZ, sN, (const double *)h->tab.p);
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((plsk::synth_y_kernel<T>), grid, dim3(plsk::WG), 0, h->stream, (T *)Y, ldy, row0, nrows, (int)M, sZ, sN,
+                           (const double *)h->tab.p);
+    });
     LAUNCH_CHECK(h);
     return PLS_HIP_OK;
 }
