@@ -98,7 +98,16 @@ typedef enum { PLS_HIP_MEM_HOST = 0, PLS_HIP_MEM_DEVICE = 1 } pls_hip_mem;
  *           Q, tt and ssy, one wide product X^T [...] per round for R and for B, any K (see there).  pls_hip_fit_resampled on
  *           such a handle runs every row-weighted replicate (bootstrap, jack-knife) from the same G (see there).
  *           pls_hip_cv_press_batch on such a handle runs the cross-validation folds of every problem from the same G and
- *           reduces PRESS on the device: one sweep over X for a whole Q^2 permutation test (see there). */
+ *           reduces PRESS on the device: one sweep over X for a whole Q^2 permutation test (see there).
+ *
+ * Accuracy (measured: INTEGRATION.md section I, "Accuracy on hard data").  On column-centred data every plan returns B within
+ * 1e-10 (relative Frobenius; 2e-5 with fp32 storage) of an extended-precision fit.  The forms that work from X^T X or X X^T
+ * -- GRAM, KERNEL_TYPE2, the single-launch X^T X fit AUTO picks for mid-size data, the host-memory entry under AUTO / GRAM,
+ * pls_hip_fit_batch, pls_hip_cv_folds on its batched route, everything under DUAL -- square the condition number of X: on
+ * uncentred or nearly rank-deficient X they lose what that algebra loses in plain fp64 on a CPU (B to 1e-7 .. 7e-6 with
+ * column means of 1e4 on unit-scale data, where KERNEL and NIPALS keep 1e-11), and no more: every route stays within a
+ * factor 10 of the CPU restatement of its own form.  The library centres nothing, and AUTO chooses by shape alone: it does
+ * not look at the data.  Centre the columns, or ask for KERNEL / NIPALS, when the means are large against the spread. */
 typedef enum {
     PLS_HIP_ALGO_KERNEL = 0,
     PLS_HIP_ALGO_NIPALS = 1,
@@ -382,7 +391,8 @@ PLS_HIP_API int pls_hip_x_diagnostics(pls_hip_handle h, const void *X, int64_t l
  *   ssy  ssy + b*M   sum_i Y_b[i,m]^2
  * so that ESS[m,c] = sum_{a<=c} Q[m,a]^2 tt[a] and R^2 Y = ESS / ssy are host arithmetic on M*A numbers.  W, P and T are NOT
  * returned: a caller who wants them for one problem calls pls_hip_fit on (X, Y_b).  Sign convention for M > 1: that of
- * pls_hip_fit.  The algebra on X^T X squares the condition number of X.
+ * pls_hip_fit.  The algebra on X^T X squares the condition number of X: the bars of INTEGRATION.md section H hold for
+ * column-centred data; on uncentred or nearly rank-deficient X the call loses what KERNEL_TYPE2 loses (the Accuracy note above).
  * 1 <= A <= K, N >= 1 (0 on a rank of a sharded handle), M >= 1, nprob >= 1, ldx, ldy >= N, X and Ys non-NULL; anything else
  * is PLS_HIP_ERR_INVALID before anything is written.
  * mem == DEVICE: the call only enqueues work on the handle's stream.  mem == HOST: the inputs cross through the pinned staging

@@ -7,6 +7,9 @@ well-separated directions, scikit-learn's NIPALS PLSRegression(scale=False, tol=
 Inputs: the reference's own example data (tests/golden/data/*.csv, copied verbatim from
 /root/reference/{toyX,toyY,nir,octane}.csv) z-scored as src/main.cpp:24-25 does, and seeded
 synthetic matrices (generator spec in DESIGN.md) identified by (N, K, M, seed) only.
+
+python tests/golden/make_golden.py --hard-only   writes the hard/h_*.npz fixtures of tests/hard_data.py alone: hard input families
+fitted in 80-digit arithmetic (mpmath, needed by this mode only), byte-identical from run to run.
 """
 import os
 import sys
@@ -84,6 +87,8 @@ def main():
     ora = po.OracleLib()
     if len(sys.argv) > 1 and sys.argv[1] == "--twins-only":
         return twins(ora)
+    if len(sys.argv) > 1 and sys.argv[1] == "--hard-only":
+        return hard(ora)
     # --- reference example data ---------------------------------------------------------
     for name, fx, fy, A in (("toy_A2", "toyX.csv", "toyY.csv", 2), ("nir_A10", "nir.csv", "octane.csv", 10)):
         X = ora.z_scores(po.read_csv(os.path.join(DATA, fx)))
@@ -130,6 +135,162 @@ def twins(ora):
         np.savez(os.path.join(HERE, name + ".npz"), N=N, K=K, M=M, A=A, seed=po.SEED_DEFAULT, f32=int(f32), Q=c["Q"], B=B,
                  tt=(c["T"] ** 2).sum(0), col_err=col_err, x_checksum=float(np.abs(X).sum()),
                  y_checksum=float(np.abs(Y).sum()))
+
+
+# --- hard input families with an extended-precision reference (tests/hard_data.py) ---------------------------------------
+# python tests/golden/make_golden.py --hard-only      (needs mpmath; no test imports it)
+MP_DIGITS = 80
+
+
+def _mp():
+    import mpmath
+    mpmath.mp.dps = MP_DIGITS
+    return mpmath
+
+
+def _to_mp(a):
+    mp = _mp()
+    return np.vectorize(mp.mpf, otypes=[object])(np.asarray(a, dtype=np.float64))
+
+
+def _to_f64(a):
+    """every entry rounded ONCE, to nearest (float(mpf) truncates)"""
+    from mpmath import libmp
+    return np.vectorize(lambda v: libmp.to_float(v._mpf_, rnd=libmp.round_nearest), otypes=[np.float64])(a)
+
+
+def _mp_norm(v):
+    return _mp().sqrt(v.dot(v))
+
+
+def mp_direction(S):
+    """dominant_direction of oracle/pls_oracle.py: M == 1: w = S; else w = S q, q the dominant eigenvector of S^T S by
+    power iteration (in steps of (S^T S)^64, then on S^T S itself) to 1e-45, largest-|.| entry positive"""
+    mp = _mp()
+    K, M = S.shape
+    if M == 1:
+        w = S[:, 0].copy()
+        return w / _mp_norm(w)
+    G = S.T.dot(S)
+    P = G / sum(G[i, i] for i in range(M))
+    for _ in range(6):
+        P = P.dot(P)
+        P = P / sum(P[i, i] for i in range(M))
+    q = P[:, int(np.argmax([P[i, i] for i in range(M)]))].copy()
+    q = q / _mp_norm(q)
+    for it in range(100000):
+        z = (P if it % 2 == 0 else G).dot(q)      # (the last steps alternate with S^T S itself: no trace of the squaring)
+        z = z / _mp_norm(z)
+        done = max(abs(z[i] - q[i]) for i in range(M)) < mp.mpf(10) ** -45
+        q = z
+        if done and it % 2 == 1:
+            break
+    else:
+        raise AssertionError("power iteration did not converge")
+    lam = q.dot(G.dot(q))
+    assert max(abs(v) for v in (G.dot(q) - lam * q)) < mp.mpf(10) ** -44 * lam   # an eigenpair, whatever route led here
+    if q[int(np.argmax([abs(v) for v in q]))] < 0:
+        q = -q
+    w = S.dot(q)
+    return w / _mp_norm(w)
+
+
+def mp_plsr(X, Y, A, nipals=False):
+    """oracle/pls_oracle.py: plsr(method 0) / plsr_nipals on object arrays of mpf: dict(R, Q, tt)"""
+    K, M = X.shape[1], Y.shape[1]
+    zero = _mp().mpf(0)
+    P = np.full((K, A), zero, dtype=object); R = P.copy(); Q = np.full((M, A), zero, dtype=object)
+    tts = np.full(A, zero, dtype=object)
+    XY = X.T.dot(Y)
+    Xd = X.copy()
+    for i in range(A):
+        w = mp_direction(Xd.T.dot(Y) if nipals else XY)
+        r = w.copy()
+        for j in range(i):
+            r = r - P[:, j].dot(w) * R[:, j]
+        t = Xd.dot(w) if nipals else X.dot(r)
+        tt = t.dot(t)
+        p = (Xd if nipals else X).T.dot(t) / tt
+        if nipals:
+            q = Y.T.dot(t) / tt
+            Xd = Xd - np.outer(t, p)
+        else:
+            q = XY.T.dot(r) / tt
+            XY = XY - np.outer(p, q) * tt
+        P[:, i] = p; R[:, i] = r; Q[:, i] = q; tts[i] = tt
+    return dict(R=R, Q=Q, tt=tts)
+
+
+def mp_b_by_components(c):
+    A = c["R"].shape[1]
+    return [c["R"][:, :n].dot(c["Q"][:, :n].T) for n in range(1, A + 1)]
+
+
+def _mp_rel(a, b):
+    mp = _mp()
+    d = a - b
+    return mp.sqrt(sum(v * v for v in d.reshape(-1))) / mp.sqrt(sum(v * v for v in b.reshape(-1)))
+
+
+def save_npz(path, **arrays):
+    """np.savez without the time stamps: the same arrays give the same bytes"""
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_STORED) as z:
+        for name, a in arrays.items():
+            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.external_attr = 0o644 << 16
+            with z.open(info, "w", force_zip64=True) as f:
+                np.lib.format.write_array(f, np.asanyarray(a), allow_pickle=False)
+
+
+def hard_case(case):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import hard_data as hd
+    from test_dual_ref import dual_fit
+    family, N, K, M, f32 = case
+    name = hd.case_name(family, N, K, M, f32)
+    ora = po.OracleLib()
+    A = hd.A
+    X, Y = hd.hard_inputs(po, family, N, K, M, hd.SEED, f32)
+    Xm, Ym = _to_mp(X), _to_mp(Y)
+    ker = mp_plsr(Xm, Ym, A)
+    Bk = mp_b_by_components(ker)
+    # the independent check of the reference: the NIPALS form in the same arithmetic
+    Bn = mp_b_by_components(mp_plsr(Xm, Ym, A, nipals=True))
+    agree = max(_mp_rel(Bn[c], Bk[c]) for c in range(A))
+    assert agree < _mp().mpf(10) ** -30, (name, agree)
+    B2 = mp_b_by_components(mp_plsr(Xm, Ym[::-1].copy(), A))           # second response set: rows of Y reversed
+    idx = hd.fold_indices(N)
+    nf, ts = idx.shape
+    E = np.zeros((M, nf * ts, A), dtype=object)
+    for f in range(nf):
+        keep = np.ones(N, dtype=bool); keep[idx[f]] = False
+        Bf = mp_b_by_components(mp_plsr(Xm[keep], Ym[keep], A))
+        for c in range(A):
+            E[:, f * ts:(f + 1) * ts, c] = (Ym[idx[f]] - Xm[idx[f]].dot(Bf[c])).T
+    fx = dict(N=N, K=K, M=M, A=A, seed=hd.SEED, f32=int(f32), x_checksum=hd.checksum(X), y_checksum=hd.checksum(Y),
+              B_ref=np.stack([_to_f64(b) for b in Bk]), tt_ref=_to_f64(ker["tt"]), B2_ref=np.stack([_to_f64(b) for b in B2]),
+              E_ref=_to_f64(E), fold_idx=idx)
+    eb, eb2, ee = hd.measure_err_form(ora, dual_fit, X, Y, fx, f32)
+    for k in eb:
+        fx["err_form_" + k] = eb[k]
+        fx["err_form2_" + k] = eb2[k]
+        fx["err_form_E_" + k] = ee[k]
+    save_npz(os.path.join(HERE, "hard", name + ".npz"), **fx)
+    return (f"{name:32s} mp forms agree {float(agree):.1e}   err_form B " + " ".join(f"{k} {v.max():.1e}" for k, v in eb.items())
+            + "   2nd set " + " ".join(f"{k} {v.max():.1e}" for k, v in eb2.items()) + "   E " + " ".join(f"{k} {v:.1e}" for k, v in ee.items()))
+
+
+def hard(ora):
+    import multiprocessing
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import hard_data as hd
+    only = sys.argv[2:]                                     # (family names: a subset, while tuning the noise levels)
+    cases = [c for c in hd.all_cases() if not only or c[0] in only]
+    os.makedirs(os.path.join(HERE, "hard"), exist_ok=True)
+    with multiprocessing.Pool(min(len(cases), max(1, (os.cpu_count() or 2) // 2), 16)) as pool:
+        for line in pool.imap(hard_case, cases):
+            print(line, flush=True)
 
 
 if __name__ == "__main__":
