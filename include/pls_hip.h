@@ -30,6 +30,17 @@
  * A handle is not thread-safe: one caller at a time per handle (the reference's Model has no shared
  * state either; use one handle per host thread, handles are independent).
  *
+ * History: the bits a call returns are a function of its arguments (values, shapes, leading dimensions and the
+ * alignment of the pointers), of the handle's options at the time of the call and of the environment switches read by
+ * pls_hip_create -- NOT of any earlier call on this handle or on another one: not of the workspaces earlier calls
+ * sized and left behind, of calls that were refused or timed out, of options that were changed and set back, of a
+ * graph captured under PLS_HIP_OPT_GRAPH, nor of the stream the handle used before.  "Two calls with the same arguments
+ * return the same bits" below is meant in this sense.  What results may depend on besides is the device, not history:
+ * its number of compute units (launch geometry, hence summation order) and, for the calls that work through their
+ * items in rounds (fit_batch, cv_folds, fit_resampled, cv_press_batch), the free device memory where half of it is
+ * less than a round of 4 GB would take.  tests/test_gpu_history.py holds every entry point to this on one GPU;
+ * INTEGRATION.md section K lists the state a handle does keep.
+ *
  * No torch types, no C++ types, no exceptions cross this boundary; every entry point
  * returns a pls_hip_status and never calls exit().  There is NO CPU fallback: without a
  * gfx950 device every compute entry point fails with PLS_HIP_ERR_DEVICE.

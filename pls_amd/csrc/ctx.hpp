@@ -128,9 +128,52 @@ struct pls_hip_context {
     // replica guard of sharded fits (small_kernels.hpp): host-mapped flag "the ranks derived different W/P/Q/R/B"
     int *diverged = nullptr, *diverged_dev = nullptr;
     DevBuf guard;
+#ifdef PLS_HIP_TESTING
+    int poison_new = -1;  // testing/libpls_hip.so: ensure() fills every fresh block with this byte (pls_hip_test_poison_workspace); -1: off
+#endif
 };
 
+// ---- the workspaces of a handle: ONE list -------------------------------------------------------------------------------------
+// Every DevBuf member of pls_hip_context, once (tests/test_workspace_list.py holds the struct and the list to each other).
+// pls_hip_destroy frees from this list, pls_hip_test_poison_workspace of the testing build fills from it.
+//   SCRATCH(name)                 nothing in it outlives the call that wrote it: a call writes whatever it reads, so the bits it
+//                                 returns cannot depend on what an earlier call left there (tests/test_gpu_history.py fills these
+//                                 with 0xFF / 0x7F / 0x01 between calls)
+//   STATEFUL(name, keep, reason)  the first `keep` bytes (WS_ALL: the whole buffer; an expression of the handle c) carry state
+//                                 from call to call ON PURPOSE, for the reason given; INTEGRATION.md section K repeats the reasons
+#define PLS_HIP_WORKSPACES(SCRATCH, STATEFUL)                                                                                        \
+    STATEFUL(zeros, WS_ALL, "256 zero bytes, cleared once when first used and only read afterwards: the source of out-of-range rows of the LDS-DMA panels") \
+    STATEFUL(resident, 256, "two arrival counters of the resident fits, used in alternating parity (resident_launches): each launch zeroes the counter of the next; the payload behind the 256 bytes is scratch") \
+    STATEFUL(rgflags, WS_ALL, "one arrival word per workgroup of resident_gram_fit_kernel: values only grow, a launch waits for words beyond rg_epoch, which the host advances by 4 per launch") \
+    STATEFUL(gxx, c->pre_xx ? WS_ALL : 0, "X^T X accumulated during an upload, only while pre_xx points into it: from upload_accumulate to the end of the same host-memory fit") \
+    STATEFUL(gxy, c->pre_xy ? WS_ALL : 0, "X^T Y accumulated during an upload, only while pre_xy points into it: from upload_accumulate to the end of the same host-memory fit") \
+    SCRATCH(tailcnt) SCRATCH(part) SCRATCH(sspart) SCRATCH(xbpart) SCRATCH(wide1) SCRATCH(red) SCRATCH(red2) SCRATCH(xx) SCRATCH(xyp)  \
+    SCRATCH(praw) SCRATCH(xy) SCRATCH(v) SCRATCH(cs) SCRATCH(coop) SCRATCH(lm) SCRATCH(tab) SCRATCH(work)                              \
+    SCRATCH(cvidx) SCRATCH(cvx) SCRATCH(cvy) SCRATCH(cvws) SCRATCH(cve) SCRATCH(cvtx) SCRATCH(cvty) SCRATCH(cvtt) SCRATCH(cvm)         \
+    SCRATCH(cvkeep) SCRATCH(cvred)                                                                                                     \
+    SCRATCH(hX) SCRATCH(hY) SCRATCH(hT) SCRATCH(hW) SCRATCH(hP) SCRATCH(hQ) SCRATCH(hR) SCRATCH(hB) SCRATCH(hIn) SCRATCH(hOut)         \
+    SCRATCH(valout) SCRATCH(valpart) SCRATCH(vale) SCRATCH(valacc) SCRATCH(valkeys) SCRATCH(valhist)                                   \
+    SCRATCH(xdS) SCRATCH(xdQ) SCRATCH(xdPT) SCRATCH(xdred) SCRATCH(xdtv) SCRATCH(xdoQ) SCRATCH(xdoT) SCRATCH(xdoS) SCRATCH(xdsmall)    \
+    SCRATCH(bws) SCRATCH(bv) SCRATCH(bred) SCRATCH(bmsg) SCRATCH(bssy) SCRATCH(bY) SCRATCH(boR) SCRATCH(boQ) SCRATCH(bott)             \
+    SCRATCH(boB) SCRATCH(bossy)                                                                                                        \
+    SCRATCH(dG) SCRATCH(dpart) SCRATCH(dV) SCRATCH(dT) SCRATCH(dY) SCRATCH(dZ) SCRATCH(dC) SCRATCH(dscr) SCRATCH(dcv) SCRATCH(dbat)    \
+    SCRATCH(dcvb) SCRATCH(cvbpos) SCRATCH(cvbidx) SCRATCH(cvbo) SCRATCH(cvboE)                                                         \
+    SCRATCH(rsw) SCRATCH(rsB) SCRATCH(rsacc) SCRATCH(rsX) SCRATCH(rsY) SCRATCH(rsW) SCRATCH(rsoS)                                      \
+    SCRATCH(guard)
+
 namespace {
+
+constexpr size_t WS_ALL = ~(size_t)0;
+
+// f(DevBuf &, keep) for every workspace of the list; keep = the leading bytes that carry state (0 for scratch)
+template <typename F>
+void for_each_workspace(pls_hip_context *c, F &&f) {
+#define PLS_HIP_WS_SCRATCH(name) f(c->name, (size_t)0);
+#define PLS_HIP_WS_STATEFUL(name, keep, reason) f(c->name, (size_t)(keep));
+    PLS_HIP_WORKSPACES(PLS_HIP_WS_SCRATCH, PLS_HIP_WS_STATEFUL)
+#undef PLS_HIP_WS_SCRATCH
+#undef PLS_HIP_WS_STATEFUL
+}
 
 #define HIPCHK(ctx, call)                                                                  \
     do {                                                                                   \
@@ -171,6 +214,12 @@ int ensure(pls_hip_context *c, DevBuf &b, size_t bytes) {
         return fail(c, PLS_HIP_ERR_ALLOC, "hipMalloc of " + std::to_string(bytes) + " bytes failed");
     }
     b.bytes = bytes;
+#ifdef PLS_HIP_TESTING
+    if (c->poison_new >= 0) {  // a fresh block is arbitrary and usually zero: the tests want it as hostile as a stale one
+        HIPCHK(c, hipMemsetAsync(b.p, c->poison_new, bytes, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));  // (the block may be written next from the copy stream)
+    }
+#endif
     return PLS_HIP_OK;
 }
 

@@ -76,6 +76,21 @@ __attribute__((visibility("default"))) int pls_hip_test_last_turn(int *out) {
     out[0] = plsk::g_test_turn.rev; out[1] = plsk::g_test_turn.edge; out[2] = plsk::g_test_turn.ntiles; out[3] = plsk::g_test_turn.grid;
     return 0;
 }
+// Fills every scratch workspace of the handle that is allocated (ctx.hpp, PLS_HIP_WORKSPACES; behind the leading bytes a stateful
+// entry keeps) with `byte` and returns the number of bytes filled, -1 on an error.  also_new != 0: until a call with
+// also_new == 0, ensure() fills every fresh allocation with `byte` as well.
+__attribute__((visibility("default"))) long long pls_hip_test_poison_workspace(pls_hip_handle h, int byte, int also_new) {
+    if (!h || hipSetDevice(h->device) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) return -1;
+    long long filled = 0;
+    bool ok = true;
+    for_each_workspace(h, [&](DevBuf &b, size_t keep) {
+        if (!b.p || keep >= b.bytes) return;
+        ok = ok && hipMemsetAsync((char *)b.p + keep, byte & 0xFF, b.bytes - keep, h->stream) == hipSuccess;
+        filled += (long long)(b.bytes - keep);
+    });
+    h->poison_new = also_new ? (byte & 0xFF) : -1;
+    return ok && hipStreamSynchronize(h->stream) == hipSuccess ? filled : -1;
+}
 #endif
 
 int pls_hip_create(pls_hip_handle *out, int device, void *stream) {
@@ -131,19 +146,11 @@ int pls_hip_destroy(pls_hip_handle h) {
     if (!h) return PLS_HIP_OK;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    DevBuf *bufs[] = {&h->tailcnt, &h->resident, &h->rgflags, &h->zeros, &h->part, &h->sspart, &h->xbpart, &h->wide1, &h->red, &h->red2, &h->xx, &h->xyp, &h->praw, &h->xy, &h->v, &h->cs, &h->coop, &h->lm, &h->gxx, &h->gxy, &h->tab,
-                      &h->cvidx, &h->cvx, &h->cvy, &h->cvws, &h->cve, &h->cvtx, &h->cvty, &h->cvtt, &h->cvm, &h->cvkeep, &h->cvred, &h->work, &h->hX, &h->hY,
-                      &h->hT, &h->hW, &h->hP, &h->hQ, &h->hR, &h->hB, &h->hIn, &h->hOut, &h->valout, &h->valpart, &h->vale, &h->valacc, &h->valkeys,
-                      &h->valhist, &h->xdS, &h->xdQ, &h->xdPT, &h->xdred, &h->xdtv, &h->xdoQ, &h->xdoT, &h->xdoS, &h->xdsmall,
-                      &h->bws, &h->bv, &h->bred, &h->bmsg, &h->bssy, &h->bY, &h->boR, &h->boQ, &h->bott, &h->boB, &h->bossy,
-                      &h->dG, &h->dpart, &h->dV, &h->dT, &h->dY, &h->dZ, &h->dC, &h->dscr, &h->dcv, &h->dbat,
-                      &h->dcvb, &h->cvbpos, &h->cvbidx, &h->cvbo, &h->cvboE,
-                      &h->rsw, &h->rsB, &h->rsacc, &h->rsX, &h->rsY, &h->rsW, &h->rsoS};
-    for (DevBuf *b : bufs)
-        if (b->p) (void)hipFree(b->p);
+    for_each_workspace(h, [](DevBuf &b, size_t) {  // (the one list of ctx.hpp)
+        if (b.p) (void)hipFree(b.p);
+    });
     for (void *q : h->graveyard) (void)hipFree(q);
     if (h->xchg) xchg_release(h);
-    if (h->guard.p) (void)hipFree(h->guard.p);
     if (h->diverged) (void)hipHostFree(h->diverged);
     for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
     if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);

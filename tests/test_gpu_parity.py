@@ -1099,7 +1099,7 @@ def test_resident_gram_single_launch_fit(handle, oracle, po, N, K, A, dt, pad, M
 
 def test_resident_gram_fit_wait_that_runs_out_is_reported():
     """The same bounded waits in the X^T X form (AUTO): a limit of one tick ends the launch with the device error of
-    pls_hip_synchronize, and the next fit works."""
+    pls_hip_synchronize, and the next fit works: it returns the bits a fresh handle's fit does."""
     code = '''
 import os, sys
 sys.path.insert(0, %r)
@@ -1115,17 +1115,22 @@ except pls_amd.PlsHipError as e:
 del os.environ["PLS_HIP_TEST_RESIDENT_LIMIT_TICKS"]
 out = h.fit_device(X, Y, 6); h.synchronize()
 print("refit finite", bool(torch.isfinite(out["B"]).all()))
+f = pls_amd.Handle(); f.set_option(pls_amd.OPT_ALGO, pls_amd.ALGO_AUTO)
+ref = f.fit_device(X, Y, 6); f.synchronize()
+print("refit equals a fresh handle's fit", all(torch.equal(out[k], ref[k]) for k in "WPQRTB"))
 ''' % ROOT
     env = dict(os.environ, PLS_AMD_LIBRARY=os.path.join(ROOT, "pls_amd", "csrc", "testing", "libpls_hip.so"))
     r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
     assert "error 2" in r.stdout and "refit finite True" in r.stdout, r.stdout[-1500:]
+    assert "refit equals a fresh handle's fit True" in r.stdout, r.stdout[-1500:]   # bit for bit, W P Q R T B
 
 
 def test_resident_fit_wait_that_runs_out_is_reported():
     """The resident fit's workgroups wait for each other inside the launch; a wait beyond its time limit (another process holding
-    the GPU's CUs) must end, poison the results and be reported by pls_hip_synchronize -- and the next fit must work.  The limit is
-    set to one tick through the test build of the library (PLS_HIP_TEST_RESIDENT_LIMIT_TICKS is read by testing/libpls_hip.so only)."""
+    the GPU's CUs) must end, poison the results and be reported by pls_hip_synchronize -- and the next fit must work: it returns
+    the bits a fresh handle's fit does.  The limit is set to one tick through the test build of the library
+    (PLS_HIP_TEST_RESIDENT_LIMIT_TICKS is read by testing/libpls_hip.so only)."""
     code = '''
 import os, sys
 sys.path.insert(0, %r)
@@ -1141,11 +1146,15 @@ except pls_amd.PlsHipError as e:
 del os.environ["PLS_HIP_TEST_RESIDENT_LIMIT_TICKS"]
 out = h.fit_device(X, Y, 6); h.synchronize()
 print("refit finite", bool(torch.isfinite(out["B"]).all()))
+f = pls_amd.Handle()
+ref = f.fit_device(X, Y, 6); f.synchronize()
+print("refit equals a fresh handle's fit", all(torch.equal(out[k], ref[k]) for k in "WPQRTB"))
 ''' % ROOT
     env = dict(os.environ, PLS_AMD_LIBRARY=os.path.join(ROOT, "pls_amd", "csrc", "testing", "libpls_hip.so"))
     r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
     assert "error 2" in r.stdout and "refit finite True" in r.stdout, r.stdout[-1500:]
+    assert "refit equals a fresh handle's fit True" in r.stdout, r.stdout[-1500:]   # bit for bit, W P Q R T B
 
 
 @pytest.mark.parametrize("N,K,A,dt,pad", [(60, 401, 10, "f64", 0), (64, 416, 12, "f64", 3), (10, 15, 3, "f64", 0), (65, 200, 8, "f64", 1),
