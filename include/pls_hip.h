@@ -143,11 +143,14 @@ typedef enum {
                                     captured into a hipGraph on its second occurrence and replayed as ONE graph launch from the
                                     third on.  Single rank, profiling off, a stream of its own (not the default stream).  0 (default): every
                                     call enqueues its kernels */
-    PLS_HIP_OPT_VALIDATION_LDS_ROWS = 9 /* pls_hip_validation: the largest nobs whose signed-rank sums are formed by ONE workgroup per
+    PLS_HIP_OPT_VALIDATION_LDS_ROWS = 9, /* pls_hip_validation: the largest nobs whose signed-rank sums are formed by ONE workgroup per
                                     (response, alternative) pair, the column pair sorted in LDS; longer columns take the streaming
                                     radix sort.  Default (what pls_hip_get_option returns on a fresh handle): the most this device
                                     allows (16000 rows with 160 KiB of LDS per workgroup).  May be lowered, 0 = every column streams;
                                     a value above the device's own is PLS_HIP_ERR_INVALID */
+    PLS_HIP_OPT_MISSING_ITERS = 10      /* pls_hip_fit_missing, M > 1: the most iterations of a component's inner loop.  Default 500
+                                    (what pls_hip_get_option returns on a fresh handle); 1 .. 2^20, anything else is
+                                    PLS_HIP_ERR_INVALID */
 } pls_hip_option;
 
 /*
@@ -509,6 +512,62 @@ PLS_HIP_API int pls_hip_cv_press_batch(pls_hip_handle h, const void *X, int64_t 
                                        int64_t N, int64_t K, int64_t M, int64_t A, int64_t nprob,
                                        const int64_t *test_idx, int64_t test_size, int64_t num_folds, int dtype, int mem,
                                        double *PRESS, double *ssy, double *E);
+
+/* ---- X with missing values: NIPALS with the missing cells skipped --------------------------------
+ * NaN in X marks a missing cell (any payload, either sign, quiet or signalling: the result does not depend on it); obs(i,k) =
+ * X[i,k] is no NaN.  Y must be complete: it is not inspected, a NaN in Y propagates.  Every inner product over a column or a
+ * row of X runs over the observed cells only and is divided by the sum of squares of the other factor over the same cells
+ * (Wold's NIPALS, as ropls and mixOmics implement it).  For component a = 0 .. A-1 on the work copies X_a, Y_a:
+ *   u = the column of Y_a with the largest sum of squares (lowest index on ties); M = 1: u = y_a
+ *   repeat, it = 1, 2, ...
+ *     w_k = sum_{i: obs(i,k)} X_a[i,k] u_i / sum_{i: obs(i,k)} u_i^2;   w = w / |w|_2
+ *     t_i = sum_{k: obs(i,k)} X_a[i,k] w_k / sum_{k: obs(i,k)} w_k^2;   q = Y_a^T t / t^T t
+ *     M = 1: stop after it = 1.  M > 1: stop when it >= 2 and |t - t_prev|^2 <= 1e-20 |t|^2, or at it =
+ *     PLS_HIP_OPT_MISSING_ITERS; else u = Y_a q / q^T q
+ *   p_k = sum_{i: obs(i,k)} X_a[i,k] t_i / sum_{i: obs(i,k)} t_i^2
+ *   X_{a+1} = X_a - t p^T on the observed cells (a NaN stays a NaN);  Y_{a+1} = Y_a - t q^T
+ *   r_a = w_a - sum_{j<a} r_j (p_j^T w_a);   B = R Q^T
+ * All sums fp64 in a fixed order, no atomics; a quotient whose denominator is exactly 0 (no observed cell) is 0, so a row or a
+ * column without an observed cell gets zeros in T[i,:] and in W/P/R/B[k,:] and leaves everything else finite.
+ * R is DEFINED by the recursion above, not as W (P^T W)^-1: with missing cells P^T W is not triangular and the two differ (ropls
+ * and mixOmics report W (P^T W)^-1).  The recursion is the matrix for which x^T R equals the scores that sequential deflation
+ * gives a complete row x, so B is self-consistent with T.  On data without NaN this is ordinary NIPALS PLS: the outputs equal
+ * the NIPALS plan of pls_hip_fit to rounding, up to the sign of a component for M > 1.
+ * Conventions of pls_hip_fit: column-major, any ld >= rows, element-aligned pointers, both storage types (fp64 arithmetic;
+ * the work copy of X is in the storage type), both memory kinds (host through the pinned staging pipeline).  X and Y are never
+ * written.  T in the storage type.  B and iters may be NULL; iters (A values, where `mem` says): the iterations each component
+ * took (all 1 for M = 1).  1 <= A <= K, N >= 1, M >= 1, ldx, ldy, ldt >= N, X, Y, W, P, Q, R, T non-NULL; anything else is
+ * PLS_HIP_ERR_INVALID.  M > 32, or a handle with a reducer installed, returns PLS_HIP_ERR_UNSUPPORTED.  Both before anything is
+ * written.  M = 1 and PLS_HIP_MEM_DEVICE: the call only enqueues.  M > 1: the call returns after the work has completed -- the
+ * iterations are enqueued in batches of 8, every kernel of an iteration returns at once when the device convergence word is
+ * set, and the host reads that word through pinned memory after each batch.  PLS_HIP_OPT_ALGO, _FUSE, _DEFER and _GRAPH do not
+ * apply: there is one route.  Two calls with the same arguments return the same bits.
+ * Per component the work copy is read three times and written once for M = 1 (deflate + w, t, p), read 2 iters + 1 times and
+ * written once for M > 1; the first sweep reads the caller's matrix instead.  Workspace: the N x K work copy and, for short
+ * wide X, up to 1024 partial score vectors.
+ * Out of scope: row-sharded handles and groups, missing values in Y, cross-validation / resampling / x_diagnostics on data with
+ * NaN, a sample-space form.
+ */
+PLS_HIP_API int pls_hip_fit_missing(pls_hip_handle h, const void *X, int64_t ldx, const void *Y, int64_t ldy,
+                                    int64_t N, int64_t K, int64_t M, int64_t A, int dtype, int mem, double *W, double *P,
+                                    double *Q, double *R, void *T, int64_t ldt, double *B, int64_t *iters);
+
+/* Scores of rows, new or training, that may have missing cells: the sequential deflation above with the model's W and P (K x A,
+ * ld K): t_a = sum_obs x_k w_ka / sum_obs w_ka^2, then x <- x - t_a p_a, on a work copy with the fit's own sweeps.  S: N x A in
+ * the storage type.  On the training X it reproduces T; on complete rows it equals pls_hip_xb(X, R).  Fitted values are
+ * S[:, :c] Q[:, :c]^T (pls_hip_xb on S).  N >= 1, 1 <= A <= K, ldx, lds >= N, non-NULL pointers, else PLS_HIP_ERR_INVALID; a
+ * handle with a reducer installed: PLS_HIP_ERR_UNSUPPORTED.  PLS_HIP_MEM_DEVICE: the call only enqueues. */
+PLS_HIP_API int pls_hip_scores_missing(pls_hip_handle h, const void *X, int64_t ldx, int64_t N, int64_t K, int64_t A,
+                                       const double *W, const double *P, int dtype, int mem, void *S, int64_t lds);
+
+/* pls_hip_colwise_z_scores over the observed cells: nobs[k] = observed cells of column k, mean and sd = sqrt(SST / (nobs - 1))
+ * over them (one sweep), Z = (X - mean) / sd with NaN kept.  Z may be NULL or equal to X; nobs may be NULL.  A column with fewer
+ * than two observed cells (sd = NaN; none: mean = NaN too) or with zero spread (sd = 0) gets NaN throughout, as the complete-data
+ * call does for a constant column; pls_hip_fit_missing then treats it as entirely missing and it drops out of the model with
+ * w_k = p_k = B_k = 0.  Single rank only: a handle with a reducer installed returns PLS_HIP_ERR_UNSUPPORTED. */
+PLS_HIP_API int pls_hip_colwise_z_scores_missing(pls_hip_handle h, const void *X, int64_t ldx, int64_t N, int64_t K,
+                                                 int dtype, int mem, void *Z, int64_t ldz, double *mean, double *sd,
+                                                 int64_t *nobs);
 
 /* ---- synthetic inputs, generated on the device (DESIGN.md "Synthetic inputs") ------ */
 

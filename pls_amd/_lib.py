@@ -22,6 +22,7 @@ MEM_HOST, MEM_DEVICE = 0, 1
 ALGO_KERNEL, ALGO_NIPALS, ALGO_GRAM, ALGO_AUTO, ALGO_DUAL = 0, 1, 2, 3, 4
 OPT_ALGO, OPT_FUSE, OPT_PROFILE, OPT_POWER_ITERS, OPT_FUSED_GRID, OPT_WORK_LAYOUT, OPT_DEFER, OPT_GRAPH = 1, 2, 3, 4, 5, 6, 7, 8
 OPT_VALIDATION_LDS_ROWS = 9
+OPT_MISSING_ITERS = 10
 REDUCE_SLICES = 8
 XCHG_HANDLE_BYTES = 160  # PLS_HIP_XCHG_HANDLE_BYTES
 FAM_XTY, FAM_XB, FAM_DEFLATE, FAM_FUSED, FAM_SMALL, FAM_COUNT = 0, 1, 2, 3, 4, 5
@@ -82,6 +83,10 @@ PROTOTYPES = [
                                      _vp, _vp, _vp, _vp, _vp, _vp]),
     ("pls_hip_cv_press_batch", _int, [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _int, _int,
                                       _vp, _vp, _vp]),
+    ("pls_hip_fit_missing", _int, [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp, _i64,
+                                   _vp, _vp]),
+    ("pls_hip_scores_missing", _int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _int, _int, _vp, _i64]),
+    ("pls_hip_colwise_z_scores_missing", _int, [_vp, _vp, _i64, _i64, _i64, _int, _int, _vp, _i64, _vp, _vp, _vp]),
     ("pls_hip_synth_x", _int, [_vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_uint64, _int]),
     ("pls_hip_synth_y", _int, [_vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_uint64, _int]),
     # one process, several GPUs: groups and resident matrices

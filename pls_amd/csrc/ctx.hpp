@@ -39,6 +39,9 @@ struct pls_hip_context {
     DevBuf dbat;  // its batched fits (plan_dual_batch.hpp): the state of a round's problems
     DevBuf dcvb, cvbpos, cvbidx, cvbo, cvboE;  // pls_hip_cv_press_batch (plan_dual_cvbatch.hpp): the state of a round's items, pos of every fold, the test rows, host staging of [PRESS | ssy] and of E
     DevBuf rsw, rsB, rsacc, rsX, rsY, rsW, rsoS;  // pls_hip_fit_resampled (plan_resample.hpp): the state of a round's replicates (general route: of one fit), a round's B, [s1, s2, B0], the row-scaled work copies, host staging of the weights and of [B0, Bmean, Bm2]
+    DevBuf mX, mws, mit, mzo;  // pls_hip_fit_missing and its companions (plan_missing.hpp): the work copy of X, vectors and partials, host staging of iters and of [mean, sd, nobs]
+    i64 opt_missing_iters = 500;  // PLS_HIP_OPT_MISSING_ITERS
+    int *mconv_host = nullptr;    // pinned: where the host reads the convergence word of the M > 1 loop
     i64 opt_val_lds_rows = -1;  // PLS_HIP_OPT_VALIDATION_LDS_ROWS; -1 = the device's own limit
     i64 val_lds_rows_dev = -1;  // that limit, found on first use
     std::string err;
@@ -159,6 +162,7 @@ struct pls_hip_context {
     SCRATCH(dG) SCRATCH(dpart) SCRATCH(dV) SCRATCH(dT) SCRATCH(dY) SCRATCH(dZ) SCRATCH(dC) SCRATCH(dscr) SCRATCH(dcv) SCRATCH(dbat)    \
     SCRATCH(dcvb) SCRATCH(cvbpos) SCRATCH(cvbidx) SCRATCH(cvbo) SCRATCH(cvboE)                                                         \
     SCRATCH(rsw) SCRATCH(rsB) SCRATCH(rsacc) SCRATCH(rsX) SCRATCH(rsY) SCRATCH(rsW) SCRATCH(rsoS)                                      \
+    SCRATCH(mX) SCRATCH(mws) SCRATCH(mit) SCRATCH(mzo)                                                                                 \
     SCRATCH(guard)
 
 namespace {

@@ -1,0 +1,518 @@
+// missing_kernels.hpp -- NIPALS with the missing cells of X skipped (pls_hip_fit_missing, pls_hip_scores_missing,
+// pls_hip_colwise_z_scores_missing; plan_missing.hpp enqueues them).  NaN in X marks a missing cell; obs(i,k) = X[i,k] is no NaN.
+//   miss_col_kernel          num[k], den[k] = sum over the OBSERVED rows of column k of x v_i, v_i^2 (w from u, p from t); the same
+//                            template deflates on the way (x - t_prev[i] p_prev[k] in registers, stored to the work copy)
+//   miss_row_kernel          num[i], den[i] = sum over the observed columns of row i of x w_k, w_k^2 (t from w); tall X in one
+//                            pass, short wide X split over K with partials and miss_row_finish_kernel
+//   the small kernels        normalisation of w, q, t^T t, the convergence word, u = Y q / q^T q, the deflation of Y, the R recursion
+//   miss_colmoments_kernel   count, mean, M2 of the observed cells of a column in one sweep; miss_zscale_kernel scales
+// All sums fp64 and in a fixed order, no atomics; a quotient whose denominator is exactly 0 (no observed cell) is 0.  The mask
+// test is x == x: the library is built without -ffast-math, with it the test would be compiled away.
+// Every kernel of an iteration of the M > 1 loop reads the device convergence word `stop` first and returns when it is set.
+#pragma once
+#include "common.hpp"
+
+namespace plsk {
+
+constexpr int MISS_KC = 8;      // columns per workgroup of the column sweep: 2 x 8 fp64 accumulators per lane
+constexpr int MISS_MAX_M = 32;  // responses the entry point takes
+
+__device__ __forceinline__ double miss_quot(double num, double den) { return den == 0.0 ? 0.0 : num / den; }
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Column sweep.  grid = (column groups ceil(K / MISS_KC), row groups G): the layout of xty_kernel with the two grid dimensions
+// swapped (K may exceed 65,535 groups).  A workgroup walks the row chunks blockIdx.y, blockIdx.y + G, ... of WG * V rows.
+//   STORE   the (deflated) cell goes to dst (src == dst: in place; src = the caller's matrix for the first component)
+//   DEFL    x <- x - tp[i] pp[k] before it is stored and used (a NaN stays a NaN)
+//   ACC     part[blockIdx.y][k] = {sum_obs x v_i, sum_obs v_i^2} (off: pls_hip_scores_missing only deflates)
+// ------------------------------------------------------------------------------------------------------------------------------
+template <typename T, int V, bool STORE, bool DEFL, bool ACC>
+__global__ __launch_bounds__(WG) void miss_col_kernel(const T *src, i64 lds_, T *dst, i64 ldd, i64 N, int K, const double *__restrict__ v,
+                                                      const double *__restrict__ tp, const double *__restrict__ pp,
+                                                      double *__restrict__ part, const int *__restrict__ stop) {
+    constexpr int KC = MISS_KC;
+    if (stop && *stop) return;
+    __shared__ double red[WG / WAVE][2 * KC];
+    const i64 k0 = (i64)blockIdx.x * KC;
+    const int kn = (int)(K - k0 < KC ? K - k0 : KC);
+    double an[KC], ad[KC], pk[KC];
+#pragma unroll
+    for (int kc = 0; kc < KC; ++kc) {
+        an[kc] = 0.0;
+        ad[kc] = 0.0;
+        pk[kc] = (DEFL && kc < kn) ? pp[k0 + kc] : 0.0;
+    }
+    constexpr i64 CH = (i64)WG * V;
+    for (i64 c = blockIdx.y; c * CH < N; c += gridDim.y) {
+        const i64 i0 = c * CH + (i64)threadIdx.x * V;
+        if (i0 + V <= N) {
+            double vv[V], tv[V];
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                vv[j] = ACC ? v[i0 + j] : 0.0;
+                tv[j] = DEFL ? tp[i0 + j] : 0.0;
+            }
+            Pack<T, V> x[KC];
+#pragma unroll
+            for (int kc = 0; kc < KC; ++kc)
+                if (kc < kn) x[kc] = ld_pack_nt<T, V>(src + i0 + (k0 + kc) * lds_);
+#pragma unroll
+            for (int kc = 0; kc < KC; ++kc)
+                if (kc < kn) {
+#pragma unroll
+                    for (int j = 0; j < V; ++j) {
+                        double xd = (double)x[kc].v[j];
+                        if (DEFL) xd = fma(-tv[j], pk[kc], xd);
+                        if (ACC) {
+                            const bool ob = xd == xd;
+                            an[kc] = ob ? fma(xd, vv[j], an[kc]) : an[kc];
+                            ad[kc] = ob ? fma(vv[j], vv[j], ad[kc]) : ad[kc];
+                        }
+                        x[kc].v[j] = (T)xd;
+                    }
+                    if (STORE) st_pack_nt<T, V>(dst + i0 + (k0 + kc) * ldd, x[kc]);
+                }
+        } else if (i0 < N) {
+            const int nv = (int)(N - i0);
+#pragma unroll
+            for (int j = 0; j < V; ++j)
+                if (j < nv) {
+                    const double vj = ACC ? v[i0 + j] : 0.0, tj = DEFL ? tp[i0 + j] : 0.0;
+#pragma unroll
+                    for (int kc = 0; kc < KC; ++kc)
+                        if (kc < kn) {
+                            double xd = (double)src[i0 + j + (k0 + kc) * lds_];
+                            if (DEFL) xd = fma(-tj, pk[kc], xd);
+                            if (ACC) {
+                                const bool ob = xd == xd;
+                                an[kc] = ob ? fma(xd, vj, an[kc]) : an[kc];
+                                ad[kc] = ob ? fma(vj, vj, ad[kc]) : ad[kc];
+                            }
+                            if (STORE) dst[i0 + j + (k0 + kc) * ldd] = (T)xd;
+                        }
+                }
+        }
+    }
+    if (!ACC) return;
+    // workgroup reduction: butterfly per value, then waves in order
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int kc = 0; kc < KC; ++kc) {
+        const double sn = wave_sum(an[kc]), sd = wave_sum(ad[kc]);
+        if (lane == 0) {
+            red[w][2 * kc] = sn;
+            red[w][2 * kc + 1] = sd;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * KC && (int)(threadIdx.x >> 1) < kn) {
+        double s = 0.0;
+#pragma unroll
+        for (int i = 0; i < WG / WAVE; ++i) s += red[i][threadIdx.x];
+        part[((i64)blockIdx.y * K + k0) * 2 + threadIdx.x] = s;
+    }
+}
+
+// out[k] = num / den with the G partial rows added in order; sspart[blockIdx.x] = this block's sum of out[k]^2 (w only)
+__global__ __launch_bounds__(WG) void miss_col_finish_kernel(const double *__restrict__ part, int G, int K, double *__restrict__ out,
+                                                             double *__restrict__ sspart, const int *__restrict__ stop) {
+    __shared__ double smem[WG / WAVE];
+    if (stop && *stop) return;
+    const i64 k = (i64)blockIdx.x * WG + threadIdx.x;
+    double val = 0.0;
+    if (k < K) {
+        double num = 0.0, den = 0.0;
+        for (int g = 0; g < G; ++g) {
+            num += part[((i64)g * K + k) * 2];
+            den += part[((i64)g * K + k) * 2 + 1];
+        }
+        val = miss_quot(num, den);
+        out[k] = val;
+    }
+    if (sspart) {
+        const double s = block_sum<WG / WAVE>(val * val, smem);
+        if (threadIdx.x == 0) sspart[blockIdx.x] = s;
+    }
+}
+
+// w <- w / |w|_2, the nb block sums of squares added in a fixed order by every workgroup (|w| = 0: w stays 0)
+__global__ __launch_bounds__(WG) void miss_normalize_kernel(double *__restrict__ w, int K, const double *__restrict__ sspart, int nb,
+                                                            const int *__restrict__ stop) {
+    __shared__ double smem[WG / WAVE];
+    if (stop && *stop) return;
+    double s = 0.0;
+    for (int j = threadIdx.x; j < nb; j += WG) s += sspart[j];
+    const double nrm = sqrt(block_sum<WG / WAVE>(s, smem));
+    const i64 k = (i64)blockIdx.x * WG + threadIdx.x;
+    if (k < K) w[k] = miss_quot(w[k], nrm);
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Row sweep over the work copy (16-byte columns: ldx a multiple of V; the padding rows are read and never used).
+// The workgroup is RL = 1 << lrl row lanes x CL = WG / RL column lanes: lane (r, c) owns the V rows (blockIdx.x RL + r) V ... and
+// walks the columns kb + c, kb + c + CL, ... of the K range blockIdx.y; the column lanes meet in LDS in the order of c.
+//   tpart == nullptr (one K range)  t[i] = num / den
+//   else                            tpart[blockIdx.y][i] = {num, den}; miss_row_finish_kernel adds the ranges in order
+// ------------------------------------------------------------------------------------------------------------------------------
+template <typename T, int V>
+__global__ __launch_bounds__(WG) void miss_row_kernel(const T *__restrict__ X, i64 ldx, i64 N, int K, const double *__restrict__ w, int lrl,
+                                                      int kper, double *__restrict__ t, double *__restrict__ tpart,
+                                                      const int *__restrict__ stop) {
+    __shared__ double sm[WG][2 * V];
+    if (stop && *stop) return;
+    const int RL = 1 << lrl, CL = WG >> lrl;
+    const int r = threadIdx.x & (RL - 1), c = threadIdx.x >> lrl;
+    const i64 i0 = ((i64)blockIdx.x * RL + r) * V;
+    const i64 kb = (i64)blockIdx.y * kper;
+    const i64 ke = kb + kper < K ? kb + kper : K;
+    double an[V], ad[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) an[j] = ad[j] = 0.0;
+    if (i0 < N) {
+        constexpr int U = 8;  // loads in flight per lane per batch
+        i64 k = kb + c;
+        for (; k + (i64)(U - 1) * CL < ke; k += (i64)U * CL) {
+            Pack<T, V> x[U];
+            double wk[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                x[u] = ld_pack_nt<T, V>(X + i0 + (k + (i64)u * CL) * ldx);
+                wk[u] = w[k + (i64)u * CL];
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int j = 0; j < V; ++j) {
+                    const double xd = (double)x[u].v[j];
+                    const bool ob = xd == xd;
+                    an[j] = ob ? fma(xd, wk[u], an[j]) : an[j];
+                    ad[j] = ob ? fma(wk[u], wk[u], ad[j]) : ad[j];
+                }
+        }
+        for (; k < ke; k += CL) {
+            const double wk = w[k];
+            const Pack<T, V> x = ld_pack_nt<T, V>(X + i0 + k * ldx);
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                const double xd = (double)x.v[j];
+                const bool ob = xd == xd;
+                an[j] = ob ? fma(xd, wk, an[j]) : an[j];
+                ad[j] = ob ? fma(wk, wk, ad[j]) : ad[j];
+            }
+        }
+    }
+    if (CL > 1) {
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            sm[threadIdx.x][2 * j] = an[j];
+            sm[threadIdx.x][2 * j + 1] = ad[j];
+        }
+        __syncthreads();
+        if (c == 0) {
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                double sn = 0.0, sd = 0.0;
+                for (int cc = 0; cc < CL; ++cc) {
+                    sn += sm[r + cc * RL][2 * j];
+                    sd += sm[r + cc * RL][2 * j + 1];
+                }
+                an[j] = sn;
+                ad[j] = sd;
+            }
+        }
+    }
+    if (c != 0) return;
+#pragma unroll
+    for (int j = 0; j < V; ++j)
+        if (i0 + j < N) {
+            if (tpart) {
+                st_pack<double, 2>(tpart + ((i64)blockIdx.y * N + i0 + j) * 2, Pack<double, 2>{{an[j], ad[j]}});
+            } else {
+                t[i0 + j] = miss_quot(an[j], ad[j]);
+            }
+        }
+}
+
+// t[i] = num / den over the S ranges.  A workgroup owns MISS_RF_ROWS rows; range lane sl adds the ranges sl, sl + SL, ... in order
+// (SL = WG / MISS_RF_ROWS, four loads in flight), then the SL lanes of a row meet in LDS in the order of sl.
+constexpr int MISS_RF_ROWS = 16;
+__global__ __launch_bounds__(WG) void miss_row_finish_kernel(const double *__restrict__ tpart, int S, i64 N, double *__restrict__ t,
+                                                             const int *__restrict__ stop) {
+    constexpr int RR = MISS_RF_ROWS, SL = WG / RR;
+    __shared__ double sm[SL][RR][2];
+    if (stop && *stop) return;
+    const int ri = threadIdx.x % RR, sl = threadIdx.x / RR;
+    const i64 i = (i64)blockIdx.x * RR + ri;
+    double num = 0.0, den = 0.0;
+    if (i < N) {
+#pragma unroll 4
+        for (int s = sl; s < S; s += SL) {
+            const Pack<double, 2> v = ld_pack<double, 2>(tpart + ((i64)s * N + i) * 2);
+            num += v.v[0];
+            den += v.v[1];
+        }
+    }
+    sm[sl][ri][0] = num;
+    sm[sl][ri][1] = den;
+    __syncthreads();
+    if (sl != 0 || i >= N) return;
+    num = den = 0.0;
+#pragma unroll
+    for (int q = 0; q < SL; ++q) {
+        num += sm[q][ri][0];
+        den += sm[q][ri][1];
+    }
+    t[i] = miss_quot(num, den);
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// The Y side: Ya is the fp64 work copy of Y (N x M, ld N).  Row-chunked kernels run G workgroups and leave one partial row each.
+// ------------------------------------------------------------------------------------------------------------------------------
+// Ya = Y; sspart[blockIdx.x][j] = this workgroup's sum of squares of column j (M > 1: the choice of u)
+template <typename T>
+__global__ __launch_bounds__(WG) void miss_y_init_kernel(const T *__restrict__ Y, i64 ldy, i64 N, int M, double *__restrict__ Ya,
+                                                         double *__restrict__ sspart) {
+    __shared__ double smem[WG / WAVE];
+    for (int j = 0; j < M; ++j) {
+        double s = 0.0;
+        for (i64 i = (i64)blockIdx.x * WG + threadIdx.x; i < N; i += (i64)gridDim.x * WG) {
+            const double y = (double)Y[i + (i64)j * ldy];
+            Ya[i + (i64)j * N] = y;
+            s = fma(y, y, s);
+        }
+        if (sspart) {
+            s = block_sum<WG / WAVE>(s, smem);
+            if (threadIdx.x == 0) sspart[(i64)blockIdx.x * M + j] = s;
+        }
+    }
+}
+
+// Ya <- Ya - t q^T, with the sums of squares of the new columns
+__global__ __launch_bounds__(WG) void miss_y_deflate_kernel(double *__restrict__ Ya, i64 N, int M, const double *__restrict__ t,
+                                                            const double *__restrict__ q, double *__restrict__ sspart) {
+    __shared__ double smem[WG / WAVE];
+    for (int j = 0; j < M; ++j) {
+        const double qj = q[j];
+        double s = 0.0;
+        for (i64 i = (i64)blockIdx.x * WG + threadIdx.x; i < N; i += (i64)gridDim.x * WG) {
+            const double y = fma(-t[i], qj, Ya[i + (i64)j * N]);
+            Ya[i + (i64)j * N] = y;
+            s = fma(y, y, s);
+        }
+        if (sspart) {
+            s = block_sum<WG / WAVE>(s, smem);
+            if (threadIdx.x == 0) sspart[(i64)blockIdx.x * M + j] = s;
+        }
+    }
+}
+
+// One wave: the column of Ya with the largest sum of squares (lowest index on ties) -> *jstar; clears the convergence word
+__global__ __launch_bounds__(WAVE) void miss_u_pick_kernel(const double *__restrict__ sspart, int G, int M, int *__restrict__ jstar,
+                                                           int *__restrict__ stop) {
+    __shared__ double ss[MISS_MAX_M];
+    for (int j = 0; j < M; ++j) {
+        double s = 0.0;
+        for (int g = threadIdx.x; g < G; g += WAVE) s += sspart[(i64)g * M + j];
+        s = wave_sum(s);
+        if (threadIdx.x == 0) ss[j] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int best = 0;
+        for (int j = 1; j < M; ++j)
+            if (ss[j] > ss[best]) best = j;
+        *jstar = best;
+        *stop = 0;
+    }
+}
+
+__global__ __launch_bounds__(WG) void miss_u_copy_kernel(const double *__restrict__ Ya, i64 N, const int *__restrict__ jstar,
+                                                         double *__restrict__ u) {
+    const i64 i = (i64)blockIdx.x * WG + threadIdx.x;
+    if (i < N) u[i] = Ya[i + (i64)(*jstar) * N];
+}
+
+// part[blockIdx.x] = {Ya^T t (M), t^T t, |t - tprev|^2} of this workgroup's rows; tprev <- t
+__global__ __launch_bounds__(WG) void miss_yt_kernel(const double *__restrict__ Ya, i64 N, int M, const double *__restrict__ t,
+                                                     double *__restrict__ tprev, double *__restrict__ part, const int *__restrict__ stop) {
+    __shared__ double smem[WG / WAVE];
+    if (stop && *stop) return;
+    const i64 i_first = (i64)blockIdx.x * WG + threadIdx.x, step = (i64)gridDim.x * WG;
+    double *out = part + (i64)blockIdx.x * (M + 2);
+    for (int j = 0; j < M; ++j) {
+        double s = 0.0;
+        for (i64 i = i_first; i < N; i += step) s = fma(Ya[i + (i64)j * N], t[i], s);
+        s = block_sum<WG / WAVE>(s, smem);
+        if (threadIdx.x == 0) out[j] = s;
+    }
+    double tt = 0.0, dd = 0.0;
+    for (i64 i = i_first; i < N; i += step) {
+        const double ti = t[i], d = ti - tprev[i];
+        tt = fma(ti, ti, tt);
+        dd = fma(d, d, dd);
+        tprev[i] = ti;
+    }
+    tt = block_sum<WG / WAVE>(tt, smem);
+    dd = block_sum<WG / WAVE>(dd, smem);
+    if (threadIdx.x == 0) {
+        out[M] = tt;
+        out[M + 1] = dd;
+    }
+}
+
+// One wave: q = Ya^T t / t^T t -> q (a column of Q), *qq = q^T q; the end of iteration `it` of a component: done when there is one
+// response, when it >= 2 and |t - tprev|^2 <= 1e-20 t^T t, or at max_it -- then the convergence word is set and *iters = it
+__global__ __launch_bounds__(WAVE) void miss_q_kernel(const double *__restrict__ part, int G, int M, int it, int max_it,
+                                                      double *__restrict__ q, double *__restrict__ qq, int *__restrict__ stop,
+                                                      long long *__restrict__ iters) {
+    __shared__ double val[MISS_MAX_M + 2];
+    if (stop && *stop) return;
+    for (int v = 0; v < M + 2; ++v) {  // the lanes share the G partial rows of a value, then the butterfly: a fixed order
+        double s = 0.0;
+        for (int g = threadIdx.x; g < G; g += WAVE) s += part[(i64)g * (M + 2) + v];
+        s = wave_sum(s);
+        if (threadIdx.x == 0) val[v] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double tt = val[M], dd = val[M + 1];
+        double s = 0.0;
+        for (int j = 0; j < M; ++j) {
+            const double qj = miss_quot(val[j], tt);
+            q[j] = qj;
+            s = fma(qj, qj, s);
+        }
+        *qq = s;
+        const bool done = M == 1 || (it >= 2 && dd <= 1e-20 * tt) || it >= max_it;
+        if (done) {
+            if (stop) *stop = 1;
+            if (iters) *iters = it;
+        }
+    }
+}
+
+// u = Ya q / q^T q
+__global__ __launch_bounds__(WG) void miss_u_kernel(const double *__restrict__ Ya, i64 N, int M, const double *__restrict__ q,
+                                                    const double *__restrict__ qq, double *__restrict__ u, const int *__restrict__ stop) {
+    if (stop && *stop) return;
+    const i64 i = (i64)blockIdx.x * WG + threadIdx.x;
+    if (i >= N) return;
+    double s = 0.0;
+    for (int j = 0; j < M; ++j) s = fma(Ya[i + (i64)j * N], q[j], s);
+    u[i] = miss_quot(s, *qq);
+}
+
+// a column of T / S in the storage type from the fp64 scores
+template <typename T>
+__global__ __launch_bounds__(WG) void miss_store_scores_kernel(const double *__restrict__ t, i64 N, T *__restrict__ out) {
+    const i64 i = (i64)blockIdx.x * WG + threadIdx.x;
+    if (i < N) out[i] = (T)t[i];
+}
+
+// cpart[j][blockIdx.x] = this workgroup's share of p_j^T w; grid = (PB slices of K, earlier components j)
+constexpr int MISS_PW_SLICES = 32;
+__global__ __launch_bounds__(WG) void miss_pw_kernel(const double *__restrict__ P, const double *__restrict__ w, int K,
+                                                     double *__restrict__ cpart) {
+    __shared__ double smem[WG / WAVE];
+    const double *p = P + (i64)blockIdx.y * K;
+    double s = 0.0;
+#pragma unroll 4
+    for (i64 k = (i64)blockIdx.x * WG + threadIdx.x; k < K; k += (i64)gridDim.x * WG) s = fma(p[k], w[k], s);
+    s = block_sum<WG / WAVE>(s, smem);
+    if (threadIdx.x == 0) cpart[(i64)blockIdx.y * gridDim.x + blockIdx.x] = s;
+}
+
+// r_a = w_a - sum_{j < a} r_j c[j], c[j] = the PB slices of cpart[j] added in order (by every workgroup, WG components at a time)
+__global__ __launch_bounds__(WG) void miss_r_kernel(const double *__restrict__ w, const double *__restrict__ R,
+                                                    const double *__restrict__ cpart, int PB, int a, int K, double *__restrict__ r) {
+    __shared__ double cs[WG];
+    const i64 k = (i64)blockIdx.x * WG + threadIdx.x;
+    double s = k < K ? w[k] : 0.0;
+    for (int j0 = 0; j0 < a; j0 += WG) {
+        const int jn = a - j0 < WG ? a - j0 : WG;
+        if ((int)threadIdx.x < jn) {
+            double c = 0.0;
+            for (int b = 0; b < PB; ++b) c += cpart[(i64)(j0 + threadIdx.x) * PB + b];
+            cs[threadIdx.x] = c;
+        }
+        __syncthreads();
+        if (k < K)
+            for (int j = 0; j < jn; ++j) s = fma(-R[k + (i64)(j0 + j) * K], cs[j], s);
+        __syncthreads();
+    }
+    if (k < K) r[k] = s;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Column statistics over the observed cells, one sweep: every lane keeps (n, sum, sum of squares) of x - c with c its own first
+// observed value, turns them into (n, mean, M2) and the triples are merged pairwise in a fixed order (Chan et al.): lanes in
+// LDS, then the G row groups in miss_colmoments_finish_kernel.  grid = (K, G).
+// ------------------------------------------------------------------------------------------------------------------------------
+struct MissMoments {
+    double n, mean, m2;
+};
+__device__ __forceinline__ MissMoments miss_merge(const MissMoments &a, const MissMoments &b) {
+    if (b.n == 0.0) return a;
+    if (a.n == 0.0) return b;
+    const double n = a.n + b.n, d = b.mean - a.mean;
+    return {n, a.mean + d * (b.n / n), a.m2 + b.m2 + d * d * (a.n * b.n / n)};
+}
+
+template <typename T>
+__global__ __launch_bounds__(WG) void miss_colmoments_kernel(const T *__restrict__ X, i64 ldx, i64 N, int K, double *__restrict__ part) {
+    __shared__ MissMoments sm[WG];
+    const T *col = X + (i64)blockIdx.x * ldx;
+    double c = 0.0, n = 0.0, s1 = 0.0, s2 = 0.0;
+    for (i64 i = (i64)blockIdx.y * WG + threadIdx.x; i < N; i += (i64)gridDim.y * WG) {
+        const double x = (double)col[i];
+        if (x == x) {
+            if (n == 0.0) c = x;
+            const double d = x - c;
+            n += 1.0;
+            s1 += d;
+            s2 = fma(d, d, s2);
+        }
+    }
+    MissMoments m = {0.0, 0.0, 0.0};
+    if (n > 0.0) m = {n, c + s1 / n, fmax(s2 - s1 * (s1 / n), 0.0)};
+    sm[threadIdx.x] = m;
+    __syncthreads();
+    for (int h = WG / 2; h >= 1; h >>= 1) {
+        if ((int)threadIdx.x < h) sm[threadIdx.x] = miss_merge(sm[threadIdx.x], sm[threadIdx.x + h]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        double *o = part + ((i64)blockIdx.y * K + blockIdx.x) * 3;
+        o[0] = sm[0].n;
+        o[1] = sm[0].mean;
+        o[2] = sm[0].m2;
+    }
+}
+
+// mean, sd = sqrt(M2 / (nobs - 1)), nobs per column; fewer than two observed cells: sd = NaN (no observed cell: mean = NaN too)
+__global__ __launch_bounds__(WG) void miss_colmoments_finish_kernel(const double *__restrict__ part, int G, int K, double *__restrict__ mean,
+                                                                    double *__restrict__ sd, long long *__restrict__ nobs) {
+    const i64 k = (i64)blockIdx.x * WG + threadIdx.x;
+    if (k >= K) return;
+    MissMoments m = {0.0, 0.0, 0.0};
+    for (int g = 0; g < G; ++g) {
+        const double *o = part + ((i64)g * K + k) * 3;
+        m = miss_merge(m, MissMoments{o[0], o[1], o[2]});
+    }
+    const double nan = __longlong_as_double(0x7FF8000000000000LL);
+    mean[k] = m.n > 0.0 ? m.mean : nan;
+    sd[k] = m.n > 1.0 ? sqrt(m.m2 / (m.n - 1.0)) : nan;
+    if (nobs) nobs[k] = (long long)m.n;
+}
+
+// Z = (X - mean) / sd, NaN kept (Z == X: in place).  grid = (K, row groups)
+template <typename T>
+__global__ __launch_bounds__(WG) void miss_zscale_kernel(const T *X, i64 ldx, T *Z, i64 ldz, i64 N, const double *__restrict__ mean,
+                                                         const double *__restrict__ sd) {
+    const double mu = mean[blockIdx.x], s = sd[blockIdx.x];
+    const T *xc = X + (i64)blockIdx.x * ldx;
+    T *zc = Z + (i64)blockIdx.x * ldz;
+    for (i64 i = (i64)blockIdx.y * WG + threadIdx.x; i < N; i += (i64)gridDim.y * WG) zc[i] = (T)(((double)xc[i] - mu) / s);
+}
+
+}  // namespace plsk

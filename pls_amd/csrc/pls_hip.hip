@@ -40,6 +40,7 @@
 #include "dual_cvbatch_kernels.hpp"
 #include "resample_kernels.hpp"
 #include "synth_kernels.hpp"
+#include "missing_kernels.hpp"
 #include "host_pipeline.hpp"
 #include "exchange_kernels.hpp"
 
@@ -152,6 +153,7 @@ int pls_hip_destroy(pls_hip_handle h) {
     for (void *q : h->graveyard) (void)hipFree(q);
     if (h->xchg) xchg_release(h);
     if (h->diverged) (void)hipHostFree(h->diverged);
+    if (h->mconv_host) (void)hipHostFree(h->mconv_host);
     for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
     if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
     h->stager.release();
@@ -197,6 +199,10 @@ int pls_hip_set_option(pls_hip_handle h, int option, int64_t value) {
             if (value < 0 || value > val_lds_rows_device(h)) return fail(h, PLS_HIP_ERR_INVALID, "validation LDS rows out of range");
             h->opt_val_lds_rows = value;
             return PLS_HIP_OK;
+        case PLS_HIP_OPT_MISSING_ITERS:
+            if (value < 1 || value > (1 << 20)) return fail(h, PLS_HIP_ERR_INVALID, "missing iters out of range");
+            h->opt_missing_iters = value;
+            return PLS_HIP_OK;
         default: return fail(h, PLS_HIP_ERR_INVALID, "unknown option");
     }
 }
@@ -214,6 +220,7 @@ int pls_hip_get_option(pls_hip_handle h, int option, int64_t *value) {
         case PLS_HIP_OPT_WORK_LAYOUT: *value = h->opt_work_layout; return PLS_HIP_OK;
         case PLS_HIP_OPT_DEFER: *value = h->opt_defer; return PLS_HIP_OK;
         case PLS_HIP_OPT_VALIDATION_LDS_ROWS: *value = h->opt_val_lds_rows >= 0 ? h->opt_val_lds_rows : val_lds_rows_device(h); return PLS_HIP_OK;
+        case PLS_HIP_OPT_MISSING_ITERS: *value = h->opt_missing_iters; return PLS_HIP_OK;
         default: return fail(h, PLS_HIP_ERR_INVALID, "unknown option");
     }
 }
@@ -557,6 +564,7 @@ int pls_hip_sse_by_components(pls_hip_handle h, const void *S, int64_t lds, cons
 #include "plan_batch.hpp"
 #include "plan_resample.hpp"
 #include "plan_dual_cvbatch.hpp"
+#include "plan_missing.hpp"
 
 
 extern "C" {
@@ -809,6 +817,143 @@ int pls_hip_x_diagnostics(pls_hip_handle h, const void *X, int64_t ldx, int64_t 
         if (S) CHK(d2h(h, S, lds, dS, dlds, N, A, es));
         if (ssx) CHK(d2h(h, ssx, A + 1, dssx, A + 1, A + 1, 1, 8));
         if (sst) CHK(d2h(h, sst, A, dsst, A, A, 1, 8));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return PLS_HIP_OK;
+}
+
+int pls_hip_fit_missing(pls_hip_handle h, const void *X, int64_t ldx, const void *Y, int64_t ldy, int64_t N, int64_t K, int64_t M,
+                        int64_t A, int dtype, int mem, double *W, double *P, double *Q, double *R, void *T, int64_t ldt, double *B,
+                        int64_t *iters) {
+    CHK(check_handle(h));
+    if (dtype != PLS_HIP_F64 && dtype != PLS_HIP_F32) return fail(h, PLS_HIP_ERR_INVALID, "bad dtype");
+    if (mem != PLS_HIP_MEM_HOST && mem != PLS_HIP_MEM_DEVICE) return fail(h, PLS_HIP_ERR_INVALID, "bad mem kind");
+    if (N < 1 || K < 1 || M < 1 || A < 1 || A > K || !X || !Y || !W || !P || !Q || !R || !T || ldx < N || ldy < N || ldt < N)
+        return fail(h, PLS_HIP_ERR_INVALID, "bad fit_missing arguments: need N>=1, 1<=A<=K, M>=1, ld>=N, X, Y, W, P, Q, R and T");
+    if (K > (((i64)1 << 31) - 1) || M > plsk::MISS_MAX_M)
+        return fail(h, PLS_HIP_ERR_UNSUPPORTED, "fit_missing takes at most 32 responses (and K < 2^31)");
+    if (h->reducer || h->nranks > 1)
+        return fail(h, PLS_HIP_ERR_UNSUPPORTED, "fit_missing needs every row of X on one handle: not on a row-sharded handle");
+    CHK(set_device(h));
+    const size_t es = esize(dtype);
+    const void *dX = X, *dY = Y;
+    void *dT = T;
+    double *dW = W, *dP = P, *dQ = Q, *dR = R, *dB = B;
+    long long *dit = (long long *)iters;
+    i64 dldx = ldx, dldy = ldy, dldt = ldt;
+    if (mem == PLS_HIP_MEM_HOST) {
+        const i64 ldn = N + ((-N) & 3);  // 16-byte columns for either type
+        CHK(ensure(h, h->hX, (size_t)ldn * K * es));
+        CHK(ensure(h, h->hY, (size_t)ldn * M * es));
+        CHK(ensure(h, h->hT, (size_t)ldn * A * es));
+        CHK(ensure(h, h->hW, (size_t)K * A * 8));
+        CHK(ensure(h, h->hP, (size_t)K * A * 8));
+        CHK(ensure(h, h->hR, (size_t)K * A * 8));
+        CHK(ensure(h, h->hQ, (size_t)M * A * 8));
+        if (B) CHK(ensure(h, h->hB, (size_t)K * M * 8));
+        if (iters) CHK(ensure(h, h->mit, (size_t)A * 8));
+        CHK(h2d(h, h->hX.p, ldn, X, ldx, N, K, es));
+        CHK(h2d(h, h->hY.p, ldn, Y, ldy, N, M, es));
+        dX = h->hX.p; dY = h->hY.p; dT = h->hT.p;
+        dW = (double *)h->hW.p; dP = (double *)h->hP.p; dQ = (double *)h->hQ.p; dR = (double *)h->hR.p;
+        dB = B ? (double *)h->hB.p : nullptr;
+        dit = iters ? (long long *)h->mit.p : nullptr;
+        dldx = dldy = dldt = ldn;
+    }
+    begin_fit_timing(h);
+    const int rc = by_dtype(dtype, [&](auto t) {
+        using Tx = decltype(t);
+        return fit_missing_device<Tx>(h, (const Tx *)dX, dldx, (const Tx *)dY, dldy, N, (int)K, (int)M, (int)A, dW, dP, dQ, dR, (Tx *)dT, dldt,
+                                      dB, dit);
+    });
+    end_fit_timing(h);
+    if (rc != PLS_HIP_OK) return rc;
+    if (mem == PLS_HIP_MEM_HOST) {
+        CHK(d2h(h, W, K, dW, K, K, A, 8));
+        CHK(d2h(h, P, K, dP, K, K, A, 8));
+        CHK(d2h(h, R, K, dR, K, K, A, 8));
+        CHK(d2h(h, Q, M, dQ, M, M, A, 8));
+        if (B) CHK(d2h(h, B, K, dB, K, K, M, 8));
+        CHK(d2h(h, T, ldt, dT, dldt, N, A, es));
+        if (iters) CHK(d2h(h, iters, A, dit, A, A, 1, 8));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return PLS_HIP_OK;
+}
+
+int pls_hip_scores_missing(pls_hip_handle h, const void *X, int64_t ldx, int64_t N, int64_t K, int64_t A, const double *W, const double *P,
+                           int dtype, int mem, void *S, int64_t lds) {
+    CHK(check_handle(h));
+    if (dtype != PLS_HIP_F64 && dtype != PLS_HIP_F32) return fail(h, PLS_HIP_ERR_INVALID, "bad dtype");
+    if (mem != PLS_HIP_MEM_HOST && mem != PLS_HIP_MEM_DEVICE) return fail(h, PLS_HIP_ERR_INVALID, "bad mem kind");
+    if (N < 1 || K < 1 || A < 1 || A > K || !X || !W || !P || !S || ldx < N || lds < N)
+        return fail(h, PLS_HIP_ERR_INVALID, "bad scores_missing arguments: need N>=1, 1<=A<=K, ld>=N, X, W, P and S");
+    if (K > (((i64)1 << 31) - 1)) return fail(h, PLS_HIP_ERR_UNSUPPORTED, "scores_missing: K < 2^31");
+    if (h->reducer || h->nranks > 1)
+        return fail(h, PLS_HIP_ERR_UNSUPPORTED, "scores_missing: not on a row-sharded handle");
+    CHK(set_device(h));
+    const size_t es = esize(dtype);
+    const void *dX = X;
+    const double *dW = W, *dP = P;
+    void *dS = S;
+    i64 dldx = ldx, dlds = lds;
+    if (mem == PLS_HIP_MEM_HOST) {
+        const i64 ldn = N + ((-N) & 3);
+        CHK(ensure(h, h->hIn, (size_t)ldn * K * es));
+        CHK(ensure(h, h->hOut, (size_t)ldn * A * es));
+        CHK(ensure(h, h->hW, (size_t)K * A * 8));
+        CHK(ensure(h, h->hP, (size_t)K * A * 8));
+        CHK(h2d(h, h->hIn.p, ldn, X, ldx, N, K, es));
+        CHK(h2d(h, h->hW.p, K, W, K, K, A, 8));
+        CHK(h2d(h, h->hP.p, K, P, K, K, A, 8));
+        dX = h->hIn.p; dS = h->hOut.p; dW = (const double *)h->hW.p; dP = (const double *)h->hP.p;
+        dldx = dlds = ldn;
+    }
+    CHK(by_dtype(dtype, [&](auto t) {
+        using Tx = decltype(t);
+        return scores_missing_device<Tx>(h, (const Tx *)dX, dldx, N, (int)K, (int)A, dW, dP, (Tx *)dS, dlds);
+    }));
+    if (mem == PLS_HIP_MEM_HOST) {
+        CHK(d2h(h, S, lds, dS, dlds, N, A, es));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return PLS_HIP_OK;
+}
+
+int pls_hip_colwise_z_scores_missing(pls_hip_handle h, const void *X, int64_t ldx, int64_t N, int64_t K, int dtype, int mem, void *Z,
+                                     int64_t ldz, double *mean, double *sd, int64_t *nobs) {
+    CHK(check_handle(h));
+    if (dtype != PLS_HIP_F64 && dtype != PLS_HIP_F32) return fail(h, PLS_HIP_ERR_INVALID, "bad dtype");
+    if (mem != PLS_HIP_MEM_HOST && mem != PLS_HIP_MEM_DEVICE) return fail(h, PLS_HIP_ERR_INVALID, "bad mem kind");
+    if (N < 1 || K < 1 || !X || !mean || !sd || ldx < N || (Z && ldz < N))
+        return fail(h, PLS_HIP_ERR_INVALID, "bad z_scores_missing arguments: need N>=1, K>=1, ld>=N, X, mean and sd");
+    if (K > (((i64)1 << 31) - 1)) return fail(h, PLS_HIP_ERR_UNSUPPORTED, "z_scores_missing: K < 2^31");
+    if (h->reducer || h->nranks > 1)
+        return fail(h, PLS_HIP_ERR_UNSUPPORTED, "z_scores_missing: single rank only, not on a row-sharded handle");
+    CHK(set_device(h));
+    const size_t es = esize(dtype);
+    const void *dX = X;
+    void *dZ = Z;
+    double *dmean = mean, *dsd = sd;
+    long long *dn = (long long *)nobs;
+    i64 dldx = ldx, dldz = ldz;
+    if (mem == PLS_HIP_MEM_HOST) {
+        CHK(ensure(h, h->hIn, (size_t)N * K * es));
+        CHK(ensure(h, h->mzo, (size_t)K * 3 * 8));  // [mean, sd, nobs]
+        CHK(h2d(h, h->hIn.p, N, X, ldx, N, K, es));
+        dX = h->hIn.p; dZ = Z ? h->hIn.p : nullptr;  // scaled in place in the staging copy
+        dmean = (double *)h->mzo.p; dsd = dmean + K; dn = nobs ? (long long *)(dsd + K) : nullptr;
+        dldx = dldz = N;
+    }
+    CHK(by_dtype(dtype, [&](auto t) {
+        using Tx = decltype(t);
+        return zscores_missing_device<Tx>(h, (const Tx *)dX, dldx, N, (int)K, (Tx *)dZ, dldz, dmean, dsd, dn);
+    }));
+    if (mem == PLS_HIP_MEM_HOST) {
+        if (Z) CHK(d2h(h, Z, ldz, dZ, dldz, N, K, es));
+        CHK(d2h(h, mean, K, dmean, K, K, 1, 8));
+        CHK(d2h(h, sd, K, dsd, K, K, 1, 8));
+        if (nobs) CHK(d2h(h, nobs, K, dn, K, K, 1, 8));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     return PLS_HIP_OK;

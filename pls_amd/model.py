@@ -149,6 +149,7 @@ def _batch_view(name, a):
 
 _RESAMPLE_OUT = ("Q", "tt", "B", "B0", "Bmean", "Bm2")
 _CVB_OUT = ("PRESS", "ssy", "E")
+_MISSING_OUT = ("W", "P", "Q", "R", "T", "B", "iters")
 
 
 def bootstrap_weights(N: int, nrep: int, seed: int = 0):
@@ -645,6 +646,103 @@ class Handle:
         L.check(rc, self.h)
         return {k: v.transpose(*view[k]) for k, v in out.items()}
 
+    # ---- X with missing values -----------------------------------------------------------------------
+    def fit_missing(self, X, Y, A: int, want=("W", "P", "Q", "R", "T", "B", "iters")):
+        """NIPALS fit of X whose NaN cells are missing values (pls_hip_fit_missing): every inner product runs over the
+        observed cells only.  Y must be complete.  Returns a dict of the outputs `want` names -- W, P, R (K, A), Q (M, A), T
+        (N, A, dtype of X), B (K, M) = R Q^T, iters (A, int64: the iterations each component took) -- torch tensors on the
+        device of X for torch inputs, numpy arrays for numpy inputs.  R is the recursion r_a = w_a - sum_j r_j (p_j^T w_a),
+        not W (P^T W)^-1.  M <= 32; a handle with a reducer: PLS_HIP_ERR_UNSUPPORTED."""
+        want = set(want)
+        bad = want - set(_MISSING_OUT)
+        if bad:
+            raise L.PlsHipError(L.ERR_INVALID, f"fit_missing: unknown output(s) {sorted(bad)}")
+        if _is_torch(X):
+            X = as_colmajor(X); Y = as_colmajor(Y, X.dtype)
+            N, K = X.shape
+            M = Y.shape[1]
+            dev, f64 = X.device, torch.float64
+            W = colmajor_empty(K, A, f64, dev, ld=K); P = colmajor_empty(K, A, f64, dev, ld=K)
+            R = colmajor_empty(K, A, f64, dev, ld=K); Q = colmajor_empty(M, A, f64, dev, ld=M)
+            T = colmajor_empty(N, A, X.dtype, dev)
+            B = colmajor_empty(K, M, f64, dev, ld=K) if "B" in want else None
+            iters = torch.empty(A, dtype=torch.int64, device=dev) if "iters" in want else None
+            rc = self._lib.pls_hip_fit_missing(self.h, X.data_ptr() or None, _ld(X), Y.data_ptr() or None, _ld(Y), N, K, M, A, self._dt(X),
+                                               L.MEM_DEVICE, W.data_ptr(), P.data_ptr(), Q.data_ptr(), R.data_ptr(), T.data_ptr(), _ld(T),
+                                               B.data_ptr() if B is not None else None, iters.data_ptr() if iters is not None else None)
+            L.check(rc, self.h)
+            self._last_inputs = (X, Y)
+        else:
+            dt = np.float32 if np.asarray(X).dtype == np.float32 else np.float64
+            X = _np_f(X, dt); Y = _np_f(Y, dt)
+            N, K = X.shape
+            M = Y.shape[1]
+            W = np.zeros((K, A), order="F"); P = np.zeros((K, A), order="F")
+            R = np.zeros((K, A), order="F"); Q = np.zeros((M, A), order="F")
+            T = np.zeros((N, A), dtype=dt, order="F")
+            B = np.zeros((K, M), order="F") if "B" in want else None
+            iters = np.zeros(A, dtype=np.int64) if "iters" in want else None
+            p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
+            rc = self._lib.pls_hip_fit_missing(self.h, p(X), max(N, 1), p(Y), max(N, 1), N, K, M, A, L.F64 if dt == np.float64 else L.F32,
+                                               L.MEM_HOST, p(W), p(P), p(Q), p(R), p(T), max(N, 1), p(B), p(iters))
+            L.check(rc, self.h)
+        full = dict(W=W, P=P, Q=Q, R=R, T=T, B=B, iters=iters)
+        return {k: full[k] for k in _MISSING_OUT if k in want}
+
+    def scores_missing(self, X, W, P):
+        """Scores of rows, new or training, that may have missing cells (pls_hip_scores_missing): sequential deflation with
+        the model's W and P (K, A).  (N, A) in the dtype of X.  On complete rows it equals xb(X, R)."""
+        if _is_torch(X):
+            X = as_colmajor(X)
+            N, K = X.shape
+            A = W.shape[1]
+            Wc = colmajor_empty(K, A, torch.float64, X.device, ld=K).copy_(W)
+            Pc = colmajor_empty(K, A, torch.float64, X.device, ld=K).copy_(P)
+            S = colmajor_empty(N, A, X.dtype, X.device)
+            rc = self._lib.pls_hip_scores_missing(self.h, X.data_ptr() or None, _ld(X), N, K, A, Wc.data_ptr(), Pc.data_ptr(),
+                                                  self._dt(X), L.MEM_DEVICE, S.data_ptr(), _ld(S))
+            L.check(rc, self.h)
+            self._last_inputs = (X, Wc, Pc)
+            return S
+        dt = np.float32 if np.asarray(X).dtype == np.float32 else np.float64
+        X = _np_f(X, dt); W = _np_f(W, np.float64); P = _np_f(P, np.float64)
+        N, K = X.shape
+        A = W.shape[1]
+        S = np.zeros((N, A), dtype=dt, order="F")
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        rc = self._lib.pls_hip_scores_missing(self.h, p(X), max(N, 1), N, K, A, p(W), p(P), L.F64 if dt == np.float64 else L.F32,
+                                              L.MEM_HOST, p(S), max(N, 1))
+        L.check(rc, self.h)
+        return S
+
+    def z_scores_missing(self, X, inplace: bool = False):
+        """(Z, mean, sd, nobs) over the observed cells of each column (pls_hip_colwise_z_scores_missing): sd with nobs - 1,
+        NaN kept in Z.  A column with fewer than two observed cells, or a constant one, is NaN throughout."""
+        if _is_torch(X):
+            X = as_colmajor(X)
+            N, K = X.shape
+            Z = X if inplace else colmajor_empty(N, K, X.dtype, X.device)
+            mean = torch.empty(K, dtype=torch.float64, device=X.device)
+            sd = torch.empty(K, dtype=torch.float64, device=X.device)
+            nobs = torch.empty(K, dtype=torch.int64, device=X.device)
+            rc = self._lib.pls_hip_colwise_z_scores_missing(self.h, X.data_ptr() or None, _ld(X), N, K, self._dt(X), L.MEM_DEVICE,
+                                                            Z.data_ptr(), _ld(Z), mean.data_ptr(), sd.data_ptr(), nobs.data_ptr())
+            L.check(rc, self.h)
+            self._last_inputs = (X,)
+            return Z, mean, sd, nobs
+        dt = np.float32 if np.asarray(X).dtype == np.float32 else np.float64
+        Xf = _np_f(X, dt)
+        if inplace and Xf is not X:
+            raise L.PlsHipError(L.ERR_INVALID, "z_scores_missing: inplace needs a column-major array of float32 or float64")
+        N, K = Xf.shape
+        Z = Xf if inplace else np.zeros((N, K), dtype=dt, order="F")
+        mean = np.zeros(K); sd = np.zeros(K); nobs = np.zeros(K, dtype=np.int64)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        rc = self._lib.pls_hip_colwise_z_scores_missing(self.h, p(Xf), max(N, 1), N, K, L.F64 if dt == np.float64 else L.F32, L.MEM_HOST,
+                                                        p(Z), max(N, 1), p(mean), p(sd), p(nobs))
+        L.check(rc, self.h)
+        return Z, mean, sd, nobs
+
     def permutation_test(self, X, Y, A: int, nperm: int, perms=None, seed: int = 0, max_bytes: int = 1 << 30, cv=None):
         """Response-permutation (Y-randomisation) test: problem 0 is Y itself, problem b is Y[perms[b-1]] (rows permuted,
         the M responses of a row together), all fitted against the same X by fit_batch.  perms: (nperm, N) int64; drawn
@@ -940,7 +1038,7 @@ class Model:
     """
 
     def __init__(self, X, Y, algorithm: int = KERNEL_TYPE1, max_components: int | None = None, *,
-                 handle: Handle | None = None):
+                 handle: Handle | None = None, missing: bool = False):
         self.handle = handle or Handle()
         self._on_device = _is_torch(X)
         K = X.shape[1]
@@ -948,7 +1046,10 @@ class Model:
         self.method = algorithm
         self.W = self.P = self.R = self.Q = self.T = None
         self._X, self._Y = X, Y  # the reference keeps _X, _Y for its cross-validation methods (pls.h:250)
-        self.plsr(X, Y, algorithm)
+        if missing:  # NaN in X marks a missing cell (plsr_missing)
+            self.plsr_missing(X, Y)
+        else:
+            self.plsr(X, Y, algorithm)
 
     # void plsr(const Mat2D&, const Mat2D&, const METHOD&)  include/PLS/pls.h:199
     def plsr(self, X, Y, algorithm: int = KERNEL_TYPE1):
@@ -960,6 +1061,27 @@ class Model:
             out = self.handle.fit_host(X, Y, self.A, algorithm, dtype=dt)
         self.W, self.P, self.Q, self.R, self.T = (out[k] for k in "WPQRT")
         self._tvar_cache = None
+
+    def plsr_missing(self, X, Y):
+        """plsr for an X whose NaN cells are missing values (Handle.fit_missing): fills the members
+        plsr fills, so scores, coefficients, fitted_values and loadingsX/Y work unchanged on complete new data; rows with
+        missing cells go through scores_missing / fitted_values_missing.  Model(X, Y, missing=True) fits this way."""
+        self.method = KERNEL_TYPE1
+        out = self.handle.fit_missing(X, Y, self.A, want=("W", "P", "Q", "R", "T", "iters"))
+        self.W, self.P, self.Q, self.R, self.T = (out[k] for k in "WPQRT")
+        self.iters = out["iters"]
+        self._tvar_cache = None
+
+    def scores_missing(self, X_new, comp: int | None = None):
+        """scores of rows that may have missing cells: sequential deflation with W and P (equals scores() on complete rows)"""
+        c = self._comp(comp)
+        return self.handle.scores_missing(X_new, self.W[:, :c], self.P[:, :c])
+
+    def fitted_values_missing(self, X_new, comp: int | None = None):
+        """fitted values of rows that may have missing cells: scores_missing(X_new, comp) Q[:, :comp]^T"""
+        c = self._comp(comp)
+        Qc = self.Q[:, :c]
+        return self.handle.xb(self.scores_missing(X_new, c), Qc.t() if _is_torch(Qc) else Qc.T)
 
     def _comp(self, comp):
         comp = self.A if comp is None else int(comp)
