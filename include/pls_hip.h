@@ -114,10 +114,13 @@ typedef enum { PLS_HIP_MEM_HOST = 0, PLS_HIP_MEM_DEVICE = 1 } pls_hip_mem;
  * Accuracy (measured: INTEGRATION.md section I, "Accuracy on hard data").  On column-centred data every plan returns B within
  * 1e-10 (relative Frobenius; 2e-5 with fp32 storage) of an extended-precision fit.  The forms that work from X^T X or X X^T
  * -- GRAM, KERNEL_TYPE2, the single-launch X^T X fit AUTO picks for mid-size data, the host-memory entry under AUTO / GRAM,
- * pls_hip_fit_batch, pls_hip_cv_folds on its batched route, everything under DUAL -- square the condition number of X: on
- * uncentred or nearly rank-deficient X they lose what that algebra loses in plain fp64 on a CPU (B to 1e-7 .. 7e-6 with
- * column means of 1e4 on unit-scale data, where KERNEL and NIPALS keep 1e-11), and no more: every route stays within a
- * factor 10 of the CPU restatement of its own form.  The library centres nothing, and AUTO chooses by shape alone: it does
+ * pls_hip_fit_batch, pls_hip_cv_folds on its batched route, everything under DUAL, which includes the sample-space routes
+ * of pls_hip_fit_resampled and pls_hip_cv_press_batch, and the K-space route of pls_hip_cv_press_batch -- square the
+ * condition number of X: on uncentred or nearly rank-deficient X they lose what that algebra loses in plain fp64 on a CPU
+ * (B to 1e-7 .. 7e-6 with column means of 1e4 on unit-scale data, where KERNEL and NIPALS keep 1e-11; measured for the two
+ * calls: B of a replicate 5e-11 .. 1e-7 and its standard error 7e-10 .. 4e-7 on the sample-space route, where the row-scaled
+ * refits keep 1e-11 .. 3e-8; PRESS 2e-10 .. 3e-6 relative), and no more: every route stays within a factor 10 of the CPU
+ * restatement of its own form (the two calls within 3.0).  pls_hip_fit_missing is NIPALS and keeps 1e-11 on such data.  The library centres nothing, and AUTO chooses by shape alone: it does
  * not look at the data.  Centre the columns, or ask for KERNEL / NIPALS, when the means are large against the spread. */
 typedef enum {
     PLS_HIP_ALGO_KERNEL = 0,
@@ -471,7 +474,9 @@ PLS_HIP_API int pls_hip_fit_batch(pls_hip_handle h, const void *X, int64_t ldx, 
  * is wanted without B; PLS_HIP_RESAMPLE_ROUND=n caps a round).  A workspace that does not fit even one replicate falls
  * through to the general route.
  * General route (every other handle or shape, PLS_HIP_RESAMPLE_REFIT=1): per replicate diag(s) X and diag(s) Y are written into
- * fp64 work copies (N x K, N x M) and fitted by the handle's KERNEL_TYPE1 plan; tt comes from that fit's scores.  Shapes
+ * fp64 work copies (N x K, N x M) and fitted by the handle's KERNEL_TYPE1 plan (a handle under PLS_HIP_ALGO_DUAL refits under
+ * PLS_HIP_ALGO_KERNEL: the route is the cross-check of the sample-space one and does not share its algebra); tt comes from
+ * that fit's scores.  Shapes
  * pls_hip_fit refuses return its status; a work copy that does not fit returns PLS_HIP_ERR_ALLOC.
  */
 PLS_HIP_API int pls_hip_fit_resampled(pls_hip_handle h, const void *X, int64_t ldx, const void *Y, int64_t ldy,

@@ -445,17 +445,20 @@ __global__ __launch_bounds__(WG) void miss_r_kernel(const double *__restrict__ w
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // Column statistics over the observed cells, one sweep: every lane keeps (n, sum, sum of squares) of x - c with c its own first
-// observed value, turns them into (n, mean, M2) and the triples are merged pairwise in a fixed order (Chan et al.): lanes in
-// LDS, then the G row groups in miss_colmoments_finish_kernel.  grid = (K, G).
+// observed value, turns them into (n, c, dm, M2) with mean = c + dm, and the partials are merged pairwise in a fixed order (Chan
+// et al.): lanes in LDS, then the G row groups in miss_colmoments_finish_kernel.  The mean stays split into its anchor c (an
+// observed value) and the small part dm until the very end: the difference of two partial means is then formed from differences
+// of data values and of small parts, not of two means rounded at eps |mean| -- on a column of 1e4 +- 1 that rounding alone costs
+// M2 four digits.  grid = (K, G).
 // ------------------------------------------------------------------------------------------------------------------------------
 struct MissMoments {
-    double n, mean, m2;
+    double n, c, dm, m2;
 };
 __device__ __forceinline__ MissMoments miss_merge(const MissMoments &a, const MissMoments &b) {
     if (b.n == 0.0) return a;
     if (a.n == 0.0) return b;
-    const double n = a.n + b.n, d = b.mean - a.mean;
-    return {n, a.mean + d * (b.n / n), a.m2 + b.m2 + d * d * (a.n * b.n / n)};
+    const double n = a.n + b.n, d = ((b.c - a.c) + b.dm) - a.dm;
+    return {n, a.c, a.dm + d * (b.n / n), a.m2 + b.m2 + d * d * (a.n * b.n / n)};
 }
 
 template <typename T>
@@ -473,8 +476,8 @@ __global__ __launch_bounds__(WG) void miss_colmoments_kernel(const T *__restrict
             s2 = fma(d, d, s2);
         }
     }
-    MissMoments m = {0.0, 0.0, 0.0};
-    if (n > 0.0) m = {n, c + s1 / n, fmax(s2 - s1 * (s1 / n), 0.0)};
+    MissMoments m = {0.0, 0.0, 0.0, 0.0};
+    if (n > 0.0) m = {n, c, s1 / n, fmax(s2 - s1 * (s1 / n), 0.0)};
     sm[threadIdx.x] = m;
     __syncthreads();
     for (int h = WG / 2; h >= 1; h >>= 1) {
@@ -482,10 +485,11 @@ __global__ __launch_bounds__(WG) void miss_colmoments_kernel(const T *__restrict
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        double *o = part + ((i64)blockIdx.y * K + blockIdx.x) * 3;
+        double *o = part + ((i64)blockIdx.y * K + blockIdx.x) * 4;
         o[0] = sm[0].n;
-        o[1] = sm[0].mean;
-        o[2] = sm[0].m2;
+        o[1] = sm[0].c;
+        o[2] = sm[0].dm;
+        o[3] = sm[0].m2;
     }
 }
 
@@ -494,13 +498,13 @@ __global__ __launch_bounds__(WG) void miss_colmoments_finish_kernel(const double
                                                                     double *__restrict__ sd, long long *__restrict__ nobs) {
     const i64 k = (i64)blockIdx.x * WG + threadIdx.x;
     if (k >= K) return;
-    MissMoments m = {0.0, 0.0, 0.0};
+    MissMoments m = {0.0, 0.0, 0.0, 0.0};
     for (int g = 0; g < G; ++g) {
-        const double *o = part + ((i64)g * K + k) * 3;
-        m = miss_merge(m, MissMoments{o[0], o[1], o[2]});
+        const double *o = part + ((i64)g * K + k) * 4;
+        m = miss_merge(m, MissMoments{o[0], o[1], o[2], o[3]});
     }
     const double nan = __longlong_as_double(0x7FF8000000000000LL);
-    mean[k] = m.n > 0.0 ? m.mean : nan;
+    mean[k] = m.n > 0.0 ? m.c + m.dm : nan;
     sd[k] = m.n > 1.0 ? sqrt(m.m2 / (m.n - 1.0)) : nan;
     if (nobs) nobs[k] = (long long)m.n;
 }

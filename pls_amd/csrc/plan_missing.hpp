@@ -225,7 +225,7 @@ template <typename T>
 int zscores_missing_device(pls_hip_context *c, const T *X, i64 ldx, i64 N, int K, T *Z, i64 ldz, double *mean, double *sd, long long *nobs) {
     const i64 nch = (N + plsk::WG - 1) / plsk::WG;
     const int G = (int)std::min<i64>(std::min<i64>(std::max<i64>(1, (8 * (i64)c->num_cu) / K), nch), 65535);
-    CHK(ensure(c, c->mws, (size_t)G * K * 3 * 8));
+    CHK(ensure(c, c->mws, (size_t)G * K * 4 * 8));  // (n, anchor, mean - anchor, M2) per row group and column
     double *part = (double *)c->mws.p;
     const dim3 grid((unsigned)K, (unsigned)G), blk(plsk::WG);
     {

@@ -140,6 +140,10 @@ int fit_resampled_refit(pls_hip_context *c, const T *X, i64 ldx, const T *Y, i64
     if (need0) CHK(resample_accumulators(c, KM, summary, B0, s1, s2, B0d));
     const double *saved_xx = c->pre_xx, *saved_xy = c->pre_xy;  // (products of an upload belong to the unscaled rows)
     c->pre_xx = c->pre_xy = nullptr;
+    // An ALGO_DUAL handle that comes here refits under KERNEL: this route is the cross-check of the sample-space one and must
+    // not share its algebra -- the Gram matrix of the scaled rows squares the condition number exactly as X X^T does.
+    const i64 saved_algo = c->opt_algo;
+    if (saved_algo == PLS_HIP_ALGO_DUAL) c->opt_algo = PLS_HIP_ALGO_KERNEL;
     int rc = PLS_HIP_OK;
     Range r_call("pls_hip_fit_resampled (refits)");
     for (i64 b = need0 ? -1 : 0; b < nrep && rc == PLS_HIP_OK; ++b) {
@@ -162,6 +166,7 @@ int fit_resampled_refit(pls_hip_context *c, const T *X, i64 ldx, const T *Y, i64
     }
     c->pre_xx = saved_xx;
     c->pre_xy = saved_xy;
+    c->opt_algo = saved_algo;
     if (rc != PLS_HIP_OK) return rc;
     if (summary) CHK(resample_finish(c, B0d, s1, s2, KM, nrep, Bmean, Bm2));
     return PLS_HIP_OK;

@@ -8,8 +8,10 @@ Inputs: the reference's own example data (tests/golden/data/*.csv, copied verbat
 /root/reference/{toyX,toyY,nir,octane}.csv) z-scored as src/main.cpp:24-25 does, and seeded
 synthetic matrices (generator spec in DESIGN.md) identified by (N, K, M, seed) only.
 
-python tests/golden/make_golden.py --hard-only   writes the hard/h_*.npz fixtures of tests/hard_data.py alone: hard input families
-fitted in 80-digit arithmetic (mpmath, needed by this mode only), byte-identical from run to run.
+python tests/golden/make_golden.py --hard-only   writes the hard/h_*.npz and hard/e_*.npz fixtures of tests/hard_data.py alone:
+hard input families fitted in 80-digit arithmetic (mpmath, needed by this mode only), byte-identical from run to run.  h_*:
+the fits and the fold residuals; e_*: the row-weighted replicates, PRESS and ssy of both response sets, the NIPALS fit with
+missing cells and the column statistics of the masked X (about 45 CPU-minutes for all 25 cases).
 """
 import os
 import sys
@@ -243,6 +245,122 @@ def save_npz(path, **arrays):
                 np.lib.format.write_array(f, np.asanyarray(a), allow_pickle=False)
 
 
+def _mp_quot(num, den):
+    """num / den entry by entry; a quotient whose denominator is exactly 0 is 0"""
+    zero = _mp().mpf(0)
+    if np.ndim(num) == 0:
+        return zero if den == 0 else num / den
+    if np.ndim(den) == 0:
+        return np.array([zero if den == 0 else n / den for n in num], dtype=object)
+    return np.array([zero if d == 0 else n / d for n, d in zip(num, den)], dtype=object)
+
+
+def mp_fit_missing(X, Y, mask, A, tol=1e-10, max_iters=500):
+    """fit_missing_ref of tests/test_missing_ref.py on object arrays of mpf (mask: True = missing): the same algorithm, the
+    same stopping rule.  dict(R, Q, T, iters)"""
+    mp = _mp()
+    zero = mp.mpf(0)
+    N, K = X.shape
+    M = Y.shape[1]
+    O = np.where(mask, 0, 1).astype(object)            # (Python ints: exact)
+    Xa = np.where(mask, zero, X)
+    Ya = Y.copy()
+    P = np.full((K, A), zero, dtype=object); R = P.copy(); Q = np.full((M, A), zero, dtype=object)
+    T = np.full((N, A), zero, dtype=object)
+    iters = np.zeros(A, dtype=np.int64)
+    tol2 = mp.mpf(tol) * mp.mpf(tol)
+    for a in range(A):
+        u = Ya[:, int(np.argmax([Ya[:, m].dot(Ya[:, m]) for m in range(M)]))].copy()
+        t_prev, it = None, 0
+        while True:
+            it += 1
+            w = _mp_quot(Xa.T.dot(u), O.T.dot(u * u))
+            w = _mp_quot(w, mp.sqrt(w.dot(w)))
+            t = _mp_quot(Xa.dot(w), O.dot(w * w))
+            tt = t.dot(t)
+            q = _mp_quot(Ya.T.dot(t), tt)
+            if M == 1:
+                break
+            if it >= 2 and (t - t_prev).dot(t - t_prev) <= tol2 * tt:
+                break
+            if it >= max_iters:
+                break
+            t_prev = t
+            u = _mp_quot(Ya.dot(q), q.dot(q))
+        p = _mp_quot(Xa.T.dot(t), O.T.dot(t * t))
+        Xa = Xa - np.outer(t, p) * O
+        Ya = Ya - np.outer(t, q)
+        r = w.copy()
+        for j in range(a):
+            r = r - R[:, j] * P[:, j].dot(w)
+        P[:, a], R[:, a], Q[:, a], T[:, a], iters[a] = p, r, q, t, it
+    return dict(R=R, Q=Q, T=T, iters=iters)
+
+
+def entry_case(case, ora, X, Y, Xm, Ym, B0m, E1, fx):
+    """tests/golden/hard/e_<case>.npz: the 80-digit figures of the resampling, PRESS and missing-value entry points"""
+    import hard_data as hd
+    from test_dual_ref import dual_fit
+    mp = _mp()
+    family, N, K, M, f32 = case
+    A = hd.A
+    Wt = hd.resample_weights(N)
+    ex = dict(family=family, N=N, K=K, M=M, A=A, seed=hd.SEED, f32=int(f32), w_checksum=hd.checksum(Wt))
+    # resampling: per weight column the fit of (diag(s) X, diag(s) Y), s = sqrt(w); a row of weight 0 is a row of zeros
+    fits = []
+    for b in range(Wt.shape[1]):
+        keep = Wt[:, b] > 0
+        s = np.array([mp.sqrt(mp.mpf(float(v))) for v in Wt[keep, b]], dtype=object)
+        fits.append(mp_plsr(Xm[keep] * s[:, None], Ym[keep] * s[:, None], A))
+    Br = [c["R"].dot(c["Q"].T) for c in fits]
+    nrep = len(Br)
+    Bmean = sum(Br[1:], Br[0]) / nrep
+    Bm2 = sum(((B - Bmean) ** 2 for B in Br[1:]), (Br[0] - Bmean) ** 2)
+    dev2 = sum(sum(v * v for v in (B - B0m).reshape(-1)) for B in Br) / nrep
+    ex.update(Qr_ref=np.stack([_to_f64(c["Q"]) for c in fits]), ttr_ref=np.stack([_to_f64(c["tt"]) for c in fits]),
+              Br_ref=np.stack([_to_f64(B) for B in Br]), Bmean_ref=_to_f64(Bmean),
+              se_ref=_to_f64(np.vectorize(mp.sqrt, otypes=[object])(Bm2)),
+              rho=float(mp.sqrt(dev2) / mp.sqrt(sum(v * v for v in B0m.reshape(-1)))))
+    # PRESS: the folds of the second response set, and both problems' sums from the unrounded residuals
+    idx = hd.fold_indices(N)
+    nf, ts = idx.shape
+    Y2 = Ym[::-1].copy()
+    E2 = np.zeros((M, nf * ts, A), dtype=object)
+    for f in range(nf):
+        keep = np.ones(N, dtype=bool); keep[idx[f]] = False
+        Bf = mp_b_by_components(mp_plsr(Xm[keep], Y2[keep], A))
+        for c in range(A):
+            E2[:, f * ts:(f + 1) * ts, c] = (Y2[idx[f]] - Xm[idx[f]].dot(Bf[c])).T
+    held = idx.reshape(-1)
+    ex.update(E2_ref=_to_f64(E2), PRESS_ref=np.stack([_to_f64((E * E).sum(axis=1)) for E in (E1, E2)]),
+              ssy_ref=np.stack([_to_f64((Yp[held] * Yp[held]).sum(axis=0)) for Yp in (Ym, Y2)]))
+    # missing values
+    for pat in hd.MISSING_PATTERNS:
+        mask = hd.missing_mask(N, K, pat)
+        ex["mask_count_" + pat] = int(mask.sum())
+        ex["mask_checksum_" + pat] = hd.checksum(np.where(mask, X, 0.0))
+        nobs = (~mask).sum(axis=0)
+        mean = np.array([Xm[~mask[:, k], k].sum() / int(nobs[k]) for k in range(K)], dtype=object)
+        sd = np.array([mp.sqrt(((Xm[~mask[:, k], k] - mean[k]) ** 2).sum() / int(nobs[k] - 1)) if nobs[k] > 1 else mp.nan
+                       for k in range(K)], dtype=object)
+        ex.update({"zmean_ref_" + pat: _to_f64(mean), "znobs_" + pat: nobs.astype(np.int64),
+                   "zsd_ref_" + pat: np.array([float("nan") if nobs[k] < 2 else _to_f64(sd[k:k + 1])[0] for k in range(K)])})
+        if not hd.has_missing_reference(family, N, K, M):
+            continue
+        c = mp_fit_missing(Xm, Ym, mask, A)
+        ex.update({"Bm_ref_" + pat: np.stack([_to_f64(b) for b in mp_b_by_components(c)]), "Tm_ref_" + pat: _to_f64(c["T"]),
+                   "iters_ref_" + pat: c["iters"]})
+    ex.update(hd.measure_entry_forms(ora, dual_fit, X, Y, Wt, fx, ex, f32))
+    name = hd.entry_name(family, N, K, M, f32)
+    save_npz(os.path.join(HERE, "hard", name + ".npz"), **ex)
+    miss = "  ".join(f"{pat}: B {np.max(ex['err_form_m_' + pat]):.1e} T {np.max(ex['err_form_mT_' + pat]):.1e} sens "
+                     f"{ex['sens_m_' + pat]:.1e} iters {ex['iters_ref_' + pat].max()}" for pat in hd.MISSING_PATTERNS
+                     if "Bm_ref_" + pat in ex)
+    return (f"{name:32s} rho {ex['rho']:.2e}   err_form B_b kernel {ex['err_form_r_kernel']:.1e} dual {ex['err_form_r_dual']:.1e}   "
+            f"se {ex['err_form_se_kernel']:.1e} {ex['err_form_se_dual']:.1e}   Bmean {ex['err_form_Bmean_kernel']:.1e} "
+            f"{ex['err_form_Bmean_dual']:.1e}   PRESS type2 {ex['err_form_P_type2']:.1e} dual {ex['err_form_P_dual']:.1e}   {miss}")
+
+
 def hard_case(case):
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import hard_data as hd
@@ -277,7 +395,8 @@ def hard_case(case):
         fx["err_form2_" + k] = eb2[k]
         fx["err_form_E_" + k] = ee[k]
     save_npz(os.path.join(HERE, "hard", name + ".npz"), **fx)
-    return (f"{name:32s} mp forms agree {float(agree):.1e}   err_form B " + " ".join(f"{k} {v.max():.1e}" for k, v in eb.items())
+    entry = entry_case(case, ora, X, Y, Xm, Ym, Bk[A - 1], E, fx)
+    return entry + "\n" + (f"{name:32s} mp forms agree {float(agree):.1e}   err_form B " + " ".join(f"{k} {v.max():.1e}" for k, v in eb.items())
             + "   2nd set " + " ".join(f"{k} {v.max():.1e}" for k, v in eb2.items()) + "   E " + " ".join(f"{k} {v:.1e}" for k, v in ee.items()))
 
 

@@ -9,6 +9,13 @@ the oracle's kernel form, its NIPALS form, its type-2 form, dual_fit of tests/te
 on the CPU.  tests/test_hard_data_ref.py pins the fixtures to the live restatements; tests/test_gpu_hard_data.py holds every
 route of the library to max(FLOOR, 10 x err_form[its form]).
 
+The same cases carry the inputs of the entry points that are not fits of (X, Y) alone: seven columns of row weights
+(resample_weights), two layouts of missing cells (missing_mask) -- both reproducible bit for bit as well -- and, in
+tests/golden/hard/e_*.npz, the 80-digit figures of the row-weighted replicates, of PRESS and ssy over the folds of both response
+sets, of the NIPALS fit with missing cells and of the column statistics of the masked X, with the err_form of every restatement
+against them (measure_entry_forms).  tests/test_gpu_hard_entry.py holds pls_hip_fit_resampled, pls_hip_cv_press_batch,
+pls_hip_fit_missing and its companions to them.
+
 Nothing here needs a GPU or mpmath.
 """
 import os
@@ -117,6 +124,189 @@ def load_case(po, family, N, K, M, f32=False):
 def second_responses(Y):
     """the second response set of a case: Y with its rows reversed"""
     return np.asfortranarray(Y[::-1])
+
+
+
+# ---- inputs of the resampling, PRESS and missing-value entry points (tests/golden/hard/e_*.npz) ---------------------------------
+NREP = 7                       # six bootstrap draws (integer counts, rows dropping out) and one column of fractional weights
+WEIGHT_SEED = 11
+MISSING_PATTERNS = ("mcar", "blocks")
+MCAR_FRACTION, BLOCKS_FRACTION = 0.15, 0.05
+# "blocks": N -> (rows, columns) of the tile that is missing entirely, then (column kc, its one observed row), (row ir, its one
+# observed column) -- all outside the tile.  A row with one observed cell has the score x / w_k, a column with one the weight
+# x / u_i: with M > 1 the iteration is no longer a power iteration and, at 60 x 400, cycles for most positions of the two cells
+# on at least one family (fit_missing_ref in fp64: of 384 random draws 7 converged on every family).  With these positions no
+# component needs more than 52 iterations and fp64 stays within 2e-11 of the reference, which tests/test_hard_data_ref.py
+# asserts: a condition on the inputs, tuned on the CPU like the noise levels above.
+BLOCKS = {1301: ((64, 128), (16, 32), (40, 700), (900, 5)), 60: ((16, 48), (128, 192), (30, 44), (1, 6))}
+# M > 1 iterates: the 80-digit restatement is made at 60 x 400 for every family, at 1301 x 48 for these two
+MISSING_MULTI_TALL = ("offset", "collinear")
+
+
+def entry_name(family, N, K, M, f32=False):
+    return "e" + case_name(family, N, K, M, f32)[1:]
+
+
+def entry_path(family, N, K, M, f32=False):
+    return os.path.join(GOLDEN, "hard", entry_name(family, N, K, M, f32) + ".npz")
+
+
+def has_missing_reference(family, N, K, M):
+    return M == 1 or N == 60 or family in MISSING_MULTI_TALL
+
+
+def resample_weights(N):
+    """(N, 7) fp64, column-major: pls_amd.bootstrap_weights(N, 6, 11), then 0.25 + 3.75 u with u = synth_x / 32 + 1 / 2 (the
+    generator's one-column matrix lies inside (-9, 9): an exact affine step into [0, 1))"""
+    import pls_amd
+    from oracle import pls_oracle as po
+    x = np.asarray(po.synth_x(0, N, 1, SEED ^ 0x4000))[:, 0]
+    u = np.ldexp(x, -5) + 0.5
+    assert (u >= 0).all() and (u < 1).all()
+    Wt = np.concatenate([pls_amd.bootstrap_weights(N, NREP - 1, WEIGHT_SEED), (0.25 + 3.75 * u)[:, None]], axis=1)
+    return np.asfortranarray(Wt, dtype=np.float64)
+
+
+def missing_mask(N, K, pattern):
+    """(N, K) bool, True = missing.  "mcar": 15 % of the cells, uniformly at random.  "blocks": one whole 64 x 16 tile (at
+    60 x 400: 32 x 64 cells), one column and one row with a single observed cell each, and 5 % random cells on top (the two
+    single cells and the rest of their column and row are set last)"""
+    rng = np.random.default_rng([int(b) for b in f"{pattern}_{N}x{K}".encode()])
+    if pattern == "mcar":
+        return rng.random((N, K)) < MCAR_FRACTION
+    if pattern != "blocks":
+        raise ValueError(pattern)
+    (r0, r1), (k0, k1), (kc, rc), (ir, kr) = BLOCKS[N]
+    m = rng.random((N, K)) < BLOCKS_FRACTION
+    m[r0:r1, k0:k1] = True
+    m[:, kc] = True
+    m[ir, :] = True
+    m[rc, kc] = False
+    m[ir, kr] = False
+    assert (~m[:, kc]).sum() == 1 and (~m[ir, :]).sum() == 1
+    return m
+
+
+def with_missing(X, mask):
+    Xn = np.array(X, order="F")
+    Xn[mask] = np.nan
+    return Xn
+
+
+def load_entry(po, family, N, K, M, f32=False):
+    """(X, Y, Wt, fixture of the fits, fixture of the entry points) with every checksum verified"""
+    X, Y, fx = load_case(po, family, N, K, M, f32)
+    ex = np.load(entry_path(family, N, K, M, f32))
+    Wt = resample_weights(N)
+    assert checksum(Wt) == float(ex["w_checksum"]), (family, N, K, M)
+    for pat in MISSING_PATTERNS:
+        m = missing_mask(N, K, pat)
+        assert int(m.sum()) == int(ex["mask_count_" + pat]) and checksum(np.where(m, X, 0.0)) == float(ex["mask_checksum_" + pat]), pat
+    return X, Y, Wt, fx, ex
+
+
+def press_of(E):
+    """column sums of squares of fold residuals E (..., nobs, A) -> (..., A)"""
+    return (np.asarray(E) ** 2).sum(axis=-2)
+
+
+def se_of(Bm2):
+    return np.sqrt(np.maximum(np.asarray(Bm2, dtype=np.float64), 0.0))
+
+
+def resample_forms(oracle):
+    """name -> (X, Y, Wt) -> dict(Q (nrep, M, A), tt (nrep, A), B (nrep, K, M), B0, Bmean, Bm2): the oracle's kernel form on the
+    scaled rows, and the restatement of the sample-space route"""
+    from test_resample_ref import dual_resample, summaries
+
+    def kernel(X, Y, Wt):
+        def one(w):
+            s = np.sqrt(w)[:, None]
+            c = oracle.plsr(np.asfortranarray(s * X), np.asfortranarray(s * Y), A)
+            return np.asarray(c["Q"]), (np.asarray(c["T"]) ** 2).sum(axis=0), np.asarray(c["R"]) @ np.asarray(c["Q"]).T
+        B0 = one(np.ones(X.shape[0]))[2]
+        Q, tt, B = (np.stack(v) for v in zip(*[one(Wt[:, b]) for b in range(Wt.shape[1])]))
+        Bmean, Bm2 = summaries(B, B0)
+        return dict(Q=Q, tt=tt, B=B, B0=B0, Bmean=Bmean, Bm2=Bm2)
+
+    def dual(X, Y, Wt):
+        with np.errstate(all="ignore"):
+            return dual_resample(X, Y, A, Wt)
+    return {"kernel": kernel, "dual": dual}
+
+
+RESAMPLE_FIGURES = ("r", "se", "Bmean", "Q", "tt")
+
+
+def resample_errors(got, ex):
+    """RESAMPLE_FIGURES of a resampling result against the 80-digit figures of the fixture: B (the worst replicate), se =
+    sqrt(max(Bm2, 0)), Bmean by rel_fro; the worst column of Q, sign-aligned on itself; the worst relative error of t^T t"""
+    from test_resample_ref import q_column_err
+    nrep = ex["Br_ref"].shape[0]
+    eb = max(rel_fro(got["B"][b], ex["Br_ref"][b]) for b in range(nrep))
+    eq = max(float(q_column_err(got["Q"][b], ex["Qr_ref"][b]).max()) for b in range(nrep))
+    et = float((np.abs(got["tt"] - ex["ttr_ref"]) / ex["ttr_ref"]).max())
+    return np.array([eb, rel_fro(se_of(got["Bm2"]), ex["se_ref"]), rel_fro(got["Bmean"], ex["Bmean_ref"]), eq, et])
+
+
+def press_errors(P, Pref):
+    """largest entrywise |P - Pref| / Pref"""
+    return float(np.max(np.abs(np.asarray(P) - Pref) / Pref))
+
+
+def missing_errors(got, ex, pat):
+    """per component count c: the larger of rel_fro(B_c, Bm_ref[c]) and the relative error of column c of T"""
+    Bs = b_by_components(got["R"], got["Q"])
+    T = np.asarray(got["T"], dtype=np.float64)
+    Bref, Tref = ex["Bm_ref_" + pat], ex["Tm_ref_" + pat]
+    return (np.array([rel_fro(Bs[c], Bref[c]) for c in range(A)]),
+            np.array([rel_fro(T[:, c], Tref[:, c]) for c in range(A)]))
+
+
+def measure_entry_forms(oracle, dual_fit, X, Y, Wt, fx, ex, f32=False):
+    """name -> figure, every err_form_* and sens_m_* of an e_*.npz fixture: what the plain-fp64 restatements in the tree
+    achieve against the 80-digit figures, each the largest over row_orders"""
+    from test_missing_ref import fit_missing_ref, measure as missing_measure
+    N, K = X.shape
+    M = Y.shape[1]
+    out = {}
+    for name, fit in resample_forms(oracle).items():
+        e = np.max([resample_errors(fit(np.asfortranarray(X[o]), np.asfortranarray(Y[o]), np.asfortranarray(Wt[o])), ex)
+                    for o in row_orders(N)], axis=0)
+        for k, v in zip(RESAMPLE_FIGURES, e):
+            out[f"err_form_{k}_{name}"] = float(v)
+    idx = fold_indices(N)
+    fits = form_fits(oracle, dual_fit, f32)
+    Ys = (Y, second_responses(Y))
+    for name in ("type2", "dual"):
+        worst = 0.0
+        for k in range(3):
+            reorder = lambda Xt, Yt, k=k, fit=fits[name]: fit(np.asfortranarray(Xt[row_orders(Xt.shape[0])[k]]),
+                                                               np.asfortranarray(Yt[row_orders(Xt.shape[0])[k]]))
+            for p in range(2):
+                worst = max(worst, press_errors(press_of(fold_residuals(X, Ys[p], idx, reorder)), ex["PRESS_ref"][p]))
+        out["err_form_P_" + name] = worst
+    for pat in MISSING_PATTERNS:
+        if not has_missing_reference(fx_family(ex), N, K, M):
+            continue
+        Xn = with_missing(X, missing_mask(N, K, pat))
+        eb, et, its = np.zeros(A), np.zeros(A), np.zeros(A, dtype=np.int64)
+        for o in row_orders(N):
+            got = fit_missing_ref(Xn[o], Y[o], A)
+            got["T"] = got["T"][np.argsort(o)]
+            b, t = missing_errors(got, ex, pat)
+            eb, et, its = np.maximum(eb, b), np.maximum(et, t), np.maximum(its, got["iters"])
+        out["err_form_m_" + pat], out["err_form_mT_" + pat], out["iters_fp64_" + pat] = eb, et, its
+        if M > 1:
+            w = missing_measure(fit_missing_ref(Xn, Y, A), fit_missing_ref(Xn, Y, A, tol=1e-14, max_iters=5000), True)
+            out["sens_m_" + pat] = max(w["B"], w["T"])
+        else:
+            out["sens_m_" + pat] = 0.0
+    return out
+
+
+def fx_family(ex):
+    return str(ex["family"])
 
 
 def fold_residuals(X, Y, idx, fit_B):
