@@ -9,13 +9,9 @@
 #include <map>
 #include <utility>
 
-#include "xb_route.hpp"  // i64, WAVE, WG
+#include "fit_route.hpp"  // the layout predicates, RED_SLICES; with xb_route.hpp: i64, WAVE, WG
 
 namespace plsk {
-
-// slices of every reduced vector (reduce_partials_kernel, slice_tail): enough workgroups take part in a reduction, and the
-// consumers add the slices of a value in index order
-constexpr int RED_SLICES = 8;
 
 // VEC consecutive rows of one column = one 16-byte (or narrower) global access per lane.
 template <typename T, int V>

@@ -23,7 +23,7 @@
 namespace plsk {
 
 constexpr int XCHG_MAX = 16;             // members
-constexpr i64 XCHG_CAP = 1 << 16;        // doubles per message piece (512 KB)
+// (XCHG_CAP, doubles per message piece: fit_route.hpp -- the plan of a fit asks whether a component's sums fit one)
 constexpr int XCHG_THREADS = 1024;
 constexpr double XCHG_TIMEOUT_S = 30.0;  // (a peer's first fit may still be loading code objects or allocating; PLS_HIP_XCHG_TIMEOUT_S)
 

@@ -960,25 +960,6 @@ __global__ __launch_bounds__(NT, NT / 256) void retile_xty_kernel(const T *src, 
     }
 }
 
-// shared by the launchers: 16-byte aligned columns / element alignment; the span of the column groups behind one descriptor
-template <typename T>
-inline bool cols_aligned(const void *q, i64 ld) {
-    constexpr int V = 16 / sizeof(T);
-    return ((uintptr_t)q % 16 == 0) && (ld % V == 0);
-}
-template <typename T>
-inline bool elem_aligned(const void *q) { return (uintptr_t)q % sizeof(T) == 0; }
-// EDGE level of a source matrix (ld in elements) read with tiles of RP row lanes: 0 plain, 1 per-wave descriptors
-// (long columns), 2 unaligned columns; -1 = not addressable at all
-template <typename T>
-inline int edge_level(const void *q, i64 ld, int cg_all, int cg_wave) {
-    if (!elem_aligned<T>(q)) return -1;
-    const bool fits = (i64)cg_all * ld * (i64)sizeof(T) < (1ll << 31);
-    if (cols_aligned<T>(q, ld) && fits) return 0;
-    if ((i64)cg_wave * ld * (i64)sizeof(T) >= (1ll << 31)) return -1;
-    return cols_aligned<T>(q, ld) ? 1 : 2;
-}
-
 // rc as launch_fused_pass; *nb = partial rows written (<= max_rows).  M <= 8.  CGX: column groups of the SOURCE tile (32:
 // 256-byte segments; 8 / 16: the taller tiles of narrow matrices, whose copy uses the same tile height).
 template <typename T, int CGX = 32>
@@ -990,10 +971,10 @@ int launch_retile_xty(hipStream_t stream, int num_cu, const T *src, i64 lds_, co
     constexpr int CG = NT / (R / V);
     const bool nostore = dst == nullptr;
     if (nostore) { ldd = R; tsd = (i64)R * K; rdst = R; }
-    if ((!nostore && !cols_aligned<T>(dst, ldd)) || tsd % V != 0 || rdst < V || R % rdst != 0 || N < 1 || M < 1 || M > 8 || max_rows < 2 ||
-        !elem_aligned<T>(Y))
+    if ((!nostore && !cols_aligned((uintptr_t)dst, ldd, sizeof(T))) || tsd % V != 0 || rdst < V || R % rdst != 0 || N < 1 || M < 1 || M > 8 || max_rows < 2 ||
+        !elem_aligned((uintptr_t)Y, sizeof(T)))
         return 1;
-    const int edge = edge_level<T>(src, lds_, CG, WAVE / (R / V));
+    const int edge = edge_level((uintptr_t)src, lds_, sizeof(T), CG, WAVE / (R / V));
     if (edge < 0) return 1;
     if (!nostore && ((i64)(R / rdst) * tsd + (i64)CG * ldd) * (i64)sizeof(T) >= (1ll << 31)) return 1;
     const i64 Nf = N - N % V;
@@ -1066,9 +1047,9 @@ int launch_deflate_score(hipStream_t stream, int num_cu, const T *src, i64 lds_,
     constexpr int V = 16 / sizeof(T);
     constexpr int R = 256 / sizeof(T), NT = 512, CPT = 8;
     constexpr int CG = NT / (R / V);
-    if (N < 1 || max_rows < 2 || !cols_aligned<T>(dst, ldd) || !elem_aligned<T>(tprev) || !elem_aligned<T>(tout)) return 1;
+    if (N < 1 || max_rows < 2 || !cols_aligned((uintptr_t)dst, ldd, sizeof(T)) || !elem_aligned((uintptr_t)tprev, sizeof(T)) || !elem_aligned((uintptr_t)tout, sizeof(T))) return 1;
     if ((N + V) * (i64)sizeof(T) >= (1ll << 31)) return 1;  // one descriptor per score column
-    const int edge = edge_level<T>(src, lds_, CG, WAVE / (R / V));
+    const int edge = edge_level((uintptr_t)src, lds_, sizeof(T), CG, WAVE / (R / V));
     if (edge < 0 || (edge == 0 && tss % V != 0)) return 1;
     if (tsd % V != 0 || rdst < V || R % rdst != 0) return 1;
     if (((i64)(R / rdst) * tsd + (i64)CG * ldd) * (i64)sizeof(T) >= (1ll << 31)) return 1;
@@ -1148,8 +1129,8 @@ int launch_retile(hipStream_t stream, int num_cu, const T *src, i64 lds_, T *dst
     constexpr int V = 16 / sizeof(T);
     constexpr int R = 256 / sizeof(T), NT = 512, CPT = 8;
     constexpr int CG = NT / (R / V);
-    if (!cols_aligned<T>(dst, ldd) || tsd % V != 0 || rdst < V || R % rdst != 0 || N < 1) return 1;
-    const int edge = edge_level<T>(src, lds_, CG, WAVE / (R / V));
+    if (!cols_aligned((uintptr_t)dst, ldd, sizeof(T)) || tsd % V != 0 || rdst < V || R % rdst != 0 || N < 1) return 1;
+    const int edge = edge_level((uintptr_t)src, lds_, sizeof(T), CG, WAVE / (R / V));
     if (edge < 0) return 1;
     if (((i64)(R / rdst) * tsd + (i64)CG * ldd) * (i64)sizeof(T) >= (1ll << 31)) return 1;
     const i64 Nf = N - N % V;
@@ -1168,30 +1149,6 @@ int launch_retile(hipStream_t stream, int num_cu, const T *src, i64 lds_, T *dst
         launch_tail_rows(stream, a);
     }
     return 0;
-}
-
-// Will launch_deflate_score accept every deflating pass of a fit (decided once per fit, like fused_pass_mode)?
-// 0 = no, 1 = yes, 2 = yes through an EDGE instantiation (long or unaligned columns).
-template <typename T>
-int deflate_score_mode(const T *X, i64 ldx, i64 N, int K, const T *Tm, i64 ldt) {
-    constexpr int V = 16 / sizeof(T);
-    constexpr int CG = 512 / ((256 / (int)sizeof(T)) / V);
-    if (N < 1 || (size_t)K * 16 > 72 * 1024 || !elem_aligned<T>(Tm) || (N + 16) * (i64)sizeof(T) >= (1ll << 31)) return 0;
-    const int e = edge_level<T>(X, ldx, CG, 4);
-    return e < 0 ? 0 : (e == 0 ? 1 : 2);
-}
-// Can the caller's matrix be copied into short tiles (launch_retile / launch_retile_xty read it with the 256-byte-segment
-// tile) and every pass then run on the copy?  The checks of deflate_score_mode without its LDS limit on K.
-template <typename T>
-bool wide_source_ok(const T *X, i64 ldx, i64 N, const T *Tm) {
-    constexpr int V = 16 / sizeof(T);
-    constexpr int CG = 512 / ((256 / (int)sizeof(T)) / V);
-    if (N < 1 || !elem_aligned<T>(Tm) || (N + 16) * (i64)sizeof(T) >= (1ll << 31)) return false;
-    return edge_level<T>(X, ldx, CG, 4) >= 0;
-}
-template <typename T>
-bool deflate_score_covers(const T *X, i64 ldx, i64 N, int K, const T *Tm, i64 ldt) {
-    return deflate_score_mode<T>(X, ldx, N, K, Tm, ldt) != 0;
 }
 
 // Loading partials p_raw = X^T t for a matrix in (ld, ts) tile addressing -- the row-tile-major work buffer of
@@ -1253,7 +1210,7 @@ int launch_xty_tiled(hipStream_t stream, int num_cu, const T *X, i64 ldx, i64 ts
     constexpr int V = 16 / sizeof(T);
     constexpr int R = (512 / CGX) * V, NT = 512, CPT = 16;  // = tile_rows<T, CGX>()
     constexpr int CG = NT / (R / V);
-    if (!cols_aligned<T>(X, ldx) || !elem_aligned<T>(t) || tsx % V != 0 || N < 1 || max_rows < 2) return 1;
+    if (!cols_aligned((uintptr_t)X, ldx, sizeof(T)) || !elem_aligned((uintptr_t)t, sizeof(T)) || tsx % V != 0 || N < 1 || max_rows < 2) return 1;
     if ((N + V) * (i64)sizeof(T) >= (1ll << 31)) return 1;  // one descriptor per score column
     if ((i64)CG * ldx * (i64)sizeof(T) >= (1ll << 31)) return 1;
     // (X is the library's own zero-padded copy: the sweep runs to the next multiple of V rows)
@@ -1279,30 +1236,6 @@ int launch_xty_tiled(hipStream_t stream, int num_cu, const T *X, i64 ldx, i64 ts
 template <typename T, int CGX = 32>
 constexpr int tile_rows() { return (512 / CGX) * (16 / (int)sizeof(T)); }
 
-// Will launch_fused_pass accept every pass of a fit on (X, ldx) with score columns Tm + a*ldt?  (Decided once
-// per fit: the work buffer's layout depends on it.)  0 = no; 1 = yes; 2 = yes through an EDGE instantiation (columns
-// that are not 16-byte aligned, or a leading dimension whose 32 column groups do not fit one descriptor -- up to
-// 2^31 bytes per WAVE / RP = 4 columns there).  Any N >= 1: the last N % V rows are the tail kernel's.
-// Column groups of the tile that reads the caller's matrix.  32 (16 row lanes, 256-byte segments) from 257 columns on;
-// NARROW matrices take taller tiles with fewer column groups, so that a lane still has 8-16 loads in flight: 8 groups x 64
-// row lanes (128 fp64 rows, 1 KB segments) up to 128 columns, 16 x 32 up to 256.  With the 32-group tile a 64-column matrix
-// has 2 loads per lane and streams at 0.64-0.68 of peak (config-3-sized: 581 / 1,097 components/s), a 32-column one at 0.38-0.46.
-inline int tall_groups(int K) {
-    return K <= 128 ? 8 : (K <= 256 ? 16 : 32);
-}
-
-template <typename T>
-int fused_pass_mode(const T *X, i64 ldx, i64 N, int K, const T *Tm, i64 ldt) {
-    const int CG = tall_groups(K);
-    if (K > 32 * 32 || N < 1 || !elem_aligned<T>(Tm) || (N + 16) * (i64)sizeof(T) >= (1ll << 31)) return 0;
-    const int e = edge_level<T>(X, ldx, CG, CG / 8);  // (a wave holds 64 / (512 / CG) = CG / 8 column groups)
-    return e < 0 ? 0 : (e == 0 ? 1 : 2);
-}
-template <typename T>
-bool fused_pass_covers(const T *X, i64 ldx, i64 N, int K, const T *Tm, i64 ldt) {
-    return fused_pass_mode<T>(X, ldx, N, K, Tm, ldt) != 0;
-}
-
 // rc: 0 = launched, 1 = shape/alignment not covered (caller falls back to the one-product
 // kernels), <0 = launch error.  grid_hint: 0 = auto.  (ldx, tsx) / (ldd, tsd): column and tile strides.
 // rdst > 0 (with CGX = 32 and a deflating pass): the destination uses tiles of rdst rows.
@@ -1327,10 +1260,10 @@ int launch_fused_pass(hipStream_t stream, int num_cu, const T *X, i64 ldx, i64 t
     const bool defl = (tprev != nullptr);
     const bool stores = defl && store;  // the pass has a store side
     if (!stores) dst = nullptr;
-    if (!elem_aligned<T>(tout) || (defl && !elem_aligned<T>(tprev)) || (stores && !cols_aligned<T>(dst, ldd))) return 1;
+    if (!elem_aligned((uintptr_t)tout, sizeof(T)) || (defl && !elem_aligned((uintptr_t)tprev, sizeof(T))) || (stores && !cols_aligned((uintptr_t)dst, ldd, sizeof(T)))) return 1;
     // the byte span of the column groups behind one descriptor (its num_records, and every lane offset) must stay below
     // 2^31: all CG groups of the workgroup, or -- EDGE -- the WAVE / RP groups of one wave
-    int edge = edge_level<T>(X, ldx, CG, WAVE / (R / V));
+    int edge = edge_level((uintptr_t)X, ldx, sizeof(T), CG, WAVE / (R / V));
     if (edge < 0 || (edge == 0 && tsx % V != 0) || (stores && tsd % V != 0)) return 1;
     // (512 groups: 32 columns per lane only for read-only passes -- v alone is 128 KB of LDS there, p_prev would not fit)
     if (K > CG * ((CGX == 64 || CGX == 128 || CGX == 256 || CGX < 32 || (CGX == 512 && defl)) ? 16 : 32) || N < 1 || max_rows < 2) return 1;

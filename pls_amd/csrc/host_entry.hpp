@@ -103,7 +103,7 @@ int upload_accumulate(pls_hip_context *c, T *dX, i64 ldd, const T *hX, i64 ldx, 
     i64 rb = (i64)(plsh::STAGE_BYTES / ((size_t)K * es)) & ~(i64)63;
     const int nbk = (K + plsk::SYRK_TB - 1) / plsk::SYRK_TB;
     const i64 S = std::max<i64>(1, (2 * (i64)c->num_cu) / (nbk * (nbk + 1) / 2));
-    if (N < 1 || K > 4096 || M > plsk::LM_MAX || rb < 64 || !vec_ok<T>(dX, ldd, FV) || !vec_ok<T>(dY, ldy, FV) ||
+    if (N < 1 || K > 4096 || M > plsk::LM_MAX || rb < 64 || !plsk::vec_ok((uintptr_t)dX, ldd, sizeof(T), FV) || !plsk::vec_ok((uintptr_t)dY, ldy, sizeof(T), FV) ||
         ensure(c, c->red2, (size_t)plsk::RED_SLICES * KK * 8) != PLS_HIP_OK ||
         ensure(c, c->part, std::max<size_t>((size_t)S * KK, (size_t)max_partial_rows(c, rb, K) * L0) * 8) != PLS_HIP_OK ||
         ensure(c, c->red, (size_t)plsk::RED_SLICES * std::max<i64>(L0, K + 1) * 8) != PLS_HIP_OK) {

@@ -4,13 +4,8 @@
 
 namespace {
 
-template <typename T>
-bool vec_ok(const void *p, i64 ld, int vec) {
-    return ((uintptr_t)p % (sizeof(T) * vec) == 0) && (ld % vec == 0);
-}
-
 // ---- geometry -------------------------------------------------------------------------
-constexpr int XTY_KCMT = 32;  // accumulators per lane in xty_kernel
+using plsk::XTY_KCMT;  // accumulators per lane in xty_kernel (fit_route.hpp)
 constexpr int DEFL_KC = 32;
 
 struct XtyGeom {
@@ -32,12 +27,7 @@ XtyGeom xty_geom(i64 N, int K, int KC, int vec, int target_wgs, int kc_first) {
     return g;
 }
 // upper bound of partial rows any product of this fit can write
-i64 max_partial_rows(pls_hip_context *c, i64 N, int K) {
-    const int nkg32 = (K + XTY_KCMT - 1) / XTY_KCMT;
-    const i64 nch = (N + plsk::WG - 1) / plsk::WG;  // vec = 1 is the worst case
-    const i64 G = std::min<i64>(std::max<i64>(1, (8 * c->num_cu) / nkg32), std::max<i64>(nch, 1));
-    return std::max<i64>(G, std::max<i64>(8 * (i64)c->num_cu, c->opt_fused_grid));
-}
+i64 max_partial_rows(pls_hip_context *c, i64 N, int K) { return plsk::max_partial_rows(c->num_cu, c->opt_fused_grid, N, K); }
 
 // ---- typed launchers --------------------------------------------------------------------
 template <int C0, int... Cs, typename F>
@@ -65,7 +55,7 @@ template <typename T>
 int launch_xb(pls_hip_context *c, const T *X, i64 ldx, i64 N, int K, const double *Bm, i64 ldb,
               int C, T *out, i64 ldo, double *sspart, int *nss) {
     constexpr int FV = 16 / sizeof(T);
-    const plsk::XbShape shape{N, K, C, ldx, ldo, (int)sizeof(T), vec_ok<T>(X, ldx, FV), vec_ok<T>(out, ldo, FV), c->num_cu, c->env.xb4, sspart != nullptr};
+    const plsk::XbShape shape{N, K, C, ldx, ldo, (int)sizeof(T), plsk::vec_ok((uintptr_t)X, ldx, sizeof(T), FV), plsk::vec_ok((uintptr_t)out, ldo, sizeof(T), FV), c->num_cu, c->env.xb4, sspart != nullptr};
     unsigned denied = 0;
     for (int c0 = 0; c0 < C;) {
         const plsk::XbStep st = plsk::xb_next(shape, c0, denied);
@@ -173,7 +163,7 @@ template <typename T>
 int launch_xty(pls_hip_context *c, const T *X, i64 ldx, const T *Y, i64 ldy, i64 N, int K, int M,
                double *part, int *nb) {
     constexpr int FV = 16 / sizeof(T);
-    const bool wide = vec_ok<T>(X, ldx, FV) && vec_ok<T>(Y, ldy, FV);
+    const bool wide = plsk::vec_ok((uintptr_t)X, ldx, sizeof(T), FV) && plsk::vec_ok((uintptr_t)Y, ldy, sizeof(T), FV);
     // workgroups per CU aimed at: 8; 4 with 8-response tiles, whose 32 butterfly sums per workgroup want longer walks
     // (config 4, fp32: 0.55 ms at 4, 0.59 at 8, 0.77 at 32 -- tools/xty_m8.py)
     const int target = (M >= 8 ? 4 : 8) * c->num_cu;
@@ -193,7 +183,7 @@ int launch_xty(pls_hip_context *c, const T *X, i64 ldx, const T *Y, i64 ldy, i64
         int rx_nb = 0;
         // ... and 1, 2 or 4 responses up to 2,048 columns: the tile walk streams X at 0.85 of peak where xty_kernel's row chunks
         // reach 0.76 (config 3, one response: 0.708 -> 0.631 ms; 131,072 x 4,096 is faster on the chunks: tools/probe/xty1.py)
-        if (wide && ((mt == 8 && M == 8) || (mt == M && K <= 2048)) && m0 == 0 && K >= 256 && plsk::cols_aligned<T>(X, ldx) &&
+        if (wide && ((mt == 8 && M == 8) || (mt == M && K <= 2048)) && m0 == 0 && K >= 256 && plsk::cols_aligned((uintptr_t)X, ldx, sizeof(T)) &&
             plsk::launch_retile_xty<T, 32>(c->stream, c->num_cu, X, ldx, Y, ldy, (T *)nullptr, 0, 0, 0, N, K, M, part,
                                            (int)max_partial_rows(c, N, K), &rx_nb) == 0) {
             *nb = rx_nb;
@@ -218,7 +208,7 @@ template <typename T>
 int launch_deflate(pls_hip_context *c, const T *src, i64 lds, T *dst, i64 ldd, i64 N, int K,
                    const T *t, const double *p) {
     constexpr int FV = 16 / sizeof(T);
-    const bool wide = vec_ok<T>(src, lds, FV) && vec_ok<T>(dst, ldd, FV) && vec_ok<T>(t, FV, FV);
+    const bool wide = plsk::vec_ok((uintptr_t)src, lds, sizeof(T), FV) && plsk::vec_ok((uintptr_t)dst, ldd, sizeof(T), FV) && plsk::vec_ok((uintptr_t)t, FV, sizeof(T), FV);
     const int nkg = (K + DEFL_KC - 1) / DEFL_KC;
     const int vec = wide ? FV : 1;
     const i64 nch = (N + (i64)plsk::WG * vec - 1) / ((i64)plsk::WG * vec);

@@ -71,7 +71,7 @@ int miss_col_sweep(pls_hip_context *c, const MissGeom &g, const T *src, i64 lds,
                    const double *tp, const double *pp, bool store, bool defl, bool acc, const MissWs &w, double *out, bool want_ss,
                    const int *stop) {
     constexpr int FV = 16 / (int)sizeof(T);
-    const bool wide = vec_ok<T>(src, lds, FV) && (!store || vec_ok<T>(dst, ldd, FV));
+    const bool wide = plsk::vec_ok((uintptr_t)src, lds, sizeof(T), FV) && (!store || plsk::vec_ok((uintptr_t)dst, ldd, sizeof(T), FV));
     const dim3 grid((unsigned)g.nkg, (unsigned)g.G), blk(plsk::WG);
     {
         Scope s(c, store ? PLS_HIP_FAM_DEFLATE : PLS_HIP_FAM_XTY, (store ? 2 : 1) * N * (i64)K * (i64)sizeof(T) + (2 * N + 2 * (i64)K) * 8);

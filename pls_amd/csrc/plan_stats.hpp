@@ -10,7 +10,7 @@ int zscores_device(pls_hip_context *c, const T *X, i64 ldx, i64 N, i64 n_total, 
                    double *mean, double *sd) {
     constexpr int FV = 16 / sizeof(T);
     constexpr int KC = 16;
-    const bool wide = vec_ok<T>(X, ldx, FV) && (!Z || vec_ok<T>(Z, ldz, FV));
+    const bool wide = plsk::vec_ok((uintptr_t)X, ldx, sizeof(T), FV) && (!Z || plsk::vec_ok((uintptr_t)Z, ldz, sizeof(T), FV));
     const int vec = wide ? FV : 1;
     const int nkg = (K + KC - 1) / KC;
     const i64 nch = std::max<i64>(1, (N + (i64)plsk::WG * vec - 1) / ((i64)plsk::WG * vec));

@@ -80,7 +80,7 @@ int xdiag_device(pls_hip_context *c, const T *X, i64 ldx, i64 N, i64 n_total, in
                 int nss = 0;
                 CHK(launch_xb<double>(c, (const double *)X, ldx, N, K, R, K, A, ws, ldn, nullptr, &nss));
             } else {
-                const bool wide = vec_ok<T>(X, ldx, 2);
+                const bool wide = plsk::vec_ok((uintptr_t)X, ldx, sizeof(T), 2);
                 const double *RT = nullptr;
                 CHK(xdiag_transposed(c, R, K, A, &RT));
                 for (int c_lo = 0; c_lo < A; c_lo += XD_RANGE) {
@@ -93,7 +93,7 @@ int xdiag_device(pls_hip_context *c, const T *X, i64 ldx, i64 N, i64 n_total, in
     }
     // ---- the residual sweep: XD_RANGE component counts at a time
     if (need_sweep) {
-        const bool wide = vec_ok<T>(X, ldx, 2);
+        const bool wide = plsk::vec_ok((uintptr_t)X, ldx, sizeof(T), 2);
         const double *PT = nullptr;
         CHK(xdiag_transposed(c, P, K, A, &PT));
         for (int c_lo = 0; c_lo < A; c_lo += XD_RANGE) {

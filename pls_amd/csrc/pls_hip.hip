@@ -52,6 +52,7 @@ using plsk::i64;
 #include "plan_common.hpp"
 #include "launch_update.hpp"
 #include "plan_dual.hpp"
+#include "plan_fit_single.hpp"
 #include "plan_fit.hpp"
 #include "host_entry.hpp"
 #include "plan_validation.hpp"

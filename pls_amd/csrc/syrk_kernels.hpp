@@ -25,7 +25,7 @@
 
 namespace plsk {
 
-constexpr int SYRK_TB = 128;  // block tile (columns of X per panel)
+// (SYRK_TB = 128, the block tile -- columns of X per panel: fit_route.hpp, whose cost model prices the blocks)
 // per storage type: V rows per 16-byte access, slab of RB = 16*V rows (256-byte column segments), LDS row
 // count padded by 2 elements: conflict-free operand reads for 8-byte (fp64: stride 34 doubles) and 4-byte
 // (fp32: stride 66 floats) elements alike.  fp32 panels are converted to fp64 at the operand read, so
