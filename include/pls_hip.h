@@ -550,8 +550,8 @@ PLS_HIP_API int pls_hip_cv_press_batch(pls_hip_handle h, const void *X, int64_t 
  * Per component the work copy is read three times and written once for M = 1 (deflate + w, t, p), read 2 iters + 1 times and
  * written once for M > 1; the first sweep reads the caller's matrix instead.  Workspace: the N x K work copy and, for short
  * wide X, up to 1024 partial score vectors.
- * Out of scope: row-sharded handles and groups, missing values in Y, cross-validation / resampling / x_diagnostics on data with
- * NaN, a sample-space form.
+ * Out of scope: row-sharded handles and groups, missing values in Y, resampling / x_diagnostics on data with NaN, a
+ * sample-space form.  Cross-validation: pls_hip_cv_folds_missing below.
  */
 PLS_HIP_API int pls_hip_fit_missing(pls_hip_handle h, const void *X, int64_t ldx, const void *Y, int64_t ldy,
                                     int64_t N, int64_t K, int64_t M, int64_t A, int dtype, int mem, double *W, double *P,
@@ -564,6 +564,38 @@ PLS_HIP_API int pls_hip_fit_missing(pls_hip_handle h, const void *X, int64_t ldx
  * handle with a reducer installed: PLS_HIP_ERR_UNSUPPORTED.  PLS_HIP_MEM_DEVICE: the call only enqueues. */
 PLS_HIP_API int pls_hip_scores_missing(pls_hip_handle h, const void *X, int64_t ldx, int64_t N, int64_t K, int64_t A,
                                        const double *W, const double *P, int dtype, int mem, void *S, int64_t lds);
+
+/* Cross-validation folds of X with missing values: what pls_hip_cv_folds is to pls_hip_fit, for pls_hip_fit_missing.
+ * Fold f holds out the rows test_idx[f * test_size .. + test_size) (host memory, as in pls_hip_cv_folds).  Its result is BY
+ * DEFINITION what the entry points above give: pls_hip_fit_missing on the training rows -> W, P, Q;
+ * S = pls_hip_scores_missing(X_test, W, P); E_c = Y_test - S[:, :c] Q[:, :c]^T for c = 1 .. A.  The data are used as given, no
+ * centring (the convention of pls_hip_cv_folds).  E has exactly the layout pls_hip_cv_folds documents:
+ * E[m * (nobs * A) + a * nobs + f * test_size + i], nobs = num_folds * test_size; pls_hip_validation takes it unchanged.
+ * iters may be NULL; else num_folds x A values, iters[f * A + a] (all 1 for M = 1).  X, Y, E and iters follow `mem`.
+ * No rows are gathered: with m the 0/1 training mask of the fold, the algorithm of pls_hip_fit_missing runs on work copies of
+ * ALL rows, the mask entering through N-sized vectors only -- w and p accumulate against m o u and m o t, q and the stop rule
+ * see m o t, u starts from the column of Y_a with the largest sum of squares over the training rows; t is computed for every
+ * row and every row of X_a and Y_a is deflated with its own t.  A held-out row adds exact zeros to every column sum and goes
+ * through the sequential deflation of pls_hip_scores_missing; after component a its row of Y_{a+1} is E's column a.  This equals
+ * the definition to rounding (at most 8e-15 measured, relative Frobenius on E).  A column with no observed training cell in a fold has
+ * w_k = p_k = 0 there, a row with no observed cell t = 0.
+ * The folds run in rounds: as many at a time as 4 GB of workspace and half the free device memory hold (each fold has its own
+ * work copy of X), at least one; PLS_HIP_ERR_ALLOC when not even one fits.  Every kernel of the component loop is launched once
+ * per round with the fold as a grid dimension, so the launches per component do not grow with the number of folds.  M > 1: every
+ * fold has its own convergence word; the host reads "every fold of the round has stopped" through pinned memory after each 8
+ * iterations.  The masked form reads the held-out rows in the w and p sweeps too: 1 / num_folds more bytes than gathered refits.
+ * All sums fp64 in a fixed order, no atomics, the sweep geometry from (N, K, type, CU count) alone: the bits of a fold's slice
+ * of E and iters depend on X, Y, A, that fold's indices, dtype, the leading dimensions, the pointer alignment and the device --
+ * not on num_folds, the round, the other folds or the handle's history.
+ * Checks, all before anything is written.  PLS_HIP_ERR_INVALID: those of pls_hip_fit_missing, N < 2, an index out of range, an
+ * index twice within a fold, test_size < 1 or >= N, num_folds < 1 (limits: 2^22 folds of 2^20 rows).  PLS_HIP_ERR_UNSUPPORTED:
+ * M > 32, a handle with a reducer installed.  The call returns after the work has completed.  PLS_HIP_OPT_ALGO, _FUSE, _DEFER
+ * and _GRAPH do not apply; PLS_HIP_OPT_MISSING_ITERS does.  R, B and T are not produced.
+ * Out of scope: row-sharded handles and groups, NaN in Y, a PRESS-only batched form. */
+PLS_HIP_API int pls_hip_cv_folds_missing(pls_hip_handle h, const void *X, int64_t ldx, const void *Y, int64_t ldy,
+                                         int64_t N, int64_t K, int64_t M, int64_t A, const int64_t *test_idx,
+                                         int64_t test_size, int64_t num_folds, int dtype, int mem, double *E,
+                                         int64_t *iters);
 
 /* pls_hip_colwise_z_scores over the observed cells: nobs[k] = observed cells of column k, mean and sd = sqrt(SST / (nobs - 1))
  * over them (one sweep), Z = (X - mean) / sd with NaN kept.  Z may be NULL or equal to X; nobs may be NULL.  A column with fewer

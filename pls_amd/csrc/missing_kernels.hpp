@@ -9,12 +9,14 @@
 // All sums fp64 and in a fixed order, no atomics; a quotient whose denominator is exactly 0 (no observed cell) is 0.  The mask
 // test is x == x: the library is built without -ffast-math, with it the test would be compiled away.
 // Every kernel of an iteration of the M > 1 loop reads the device convergence word `stop` first and returns when it is set.
+// The sweeps, their finish and normalise kernels and the one-wave kernels of the Y side are written as *_body functions with a
+// __global__ wrapper each: missing_cv_kernels.hpp wraps the same bodies once more, with the fold of a round in blockIdx.z.
 #pragma once
 #include "common.hpp"
+#include "miss_layout.hpp"  // MISS_KC, the sweep geometry
 
 namespace plsk {
 
-constexpr int MISS_KC = 8;      // columns per workgroup of the column sweep: 2 x 8 fp64 accumulators per lane
 constexpr int MISS_MAX_M = 32;  // responses the entry point takes
 
 __device__ __forceinline__ double miss_quot(double num, double den) { return den == 0.0 ? 0.0 : num / den; }
@@ -27,9 +29,9 @@ __device__ __forceinline__ double miss_quot(double num, double den) { return den
 //   ACC     part[blockIdx.y][k] = {sum_obs x v_i, sum_obs v_i^2} (off: pls_hip_scores_missing only deflates)
 // ------------------------------------------------------------------------------------------------------------------------------
 template <typename T, int V, bool STORE, bool DEFL, bool ACC>
-__global__ __launch_bounds__(WG) void miss_col_kernel(const T *src, i64 lds_, T *dst, i64 ldd, i64 N, int K, const double *__restrict__ v,
-                                                      const double *__restrict__ tp, const double *__restrict__ pp,
-                                                      double *__restrict__ part, const int *__restrict__ stop) {
+__device__ __forceinline__ void miss_col_body(const T *src, i64 lds_, T *dst, i64 ldd, i64 N, int K, const double *__restrict__ v,
+                                              const double *__restrict__ tp, const double *__restrict__ pp,
+                                              double *__restrict__ part, const int *__restrict__ stop) {
     constexpr int KC = MISS_KC;
     if (stop && *stop) return;
     __shared__ double red[WG / WAVE][2 * KC];
@@ -112,10 +114,16 @@ __global__ __launch_bounds__(WG) void miss_col_kernel(const T *src, i64 lds_, T 
         part[((i64)blockIdx.y * K + k0) * 2 + threadIdx.x] = s;
     }
 }
+template <typename T, int V, bool STORE, bool DEFL, bool ACC>
+__global__ __launch_bounds__(WG) void miss_col_kernel(const T *src, i64 lds_, T *dst, i64 ldd, i64 N, int K, const double *__restrict__ v,
+                                                      const double *__restrict__ tp, const double *__restrict__ pp,
+                                                      double *__restrict__ part, const int *__restrict__ stop) {
+    miss_col_body<T, V, STORE, DEFL, ACC>(src, lds_, dst, ldd, N, K, v, tp, pp, part, stop);
+}
 
 // out[k] = num / den with the G partial rows added in order; sspart[blockIdx.x] = this block's sum of out[k]^2 (w only)
-__global__ __launch_bounds__(WG) void miss_col_finish_kernel(const double *__restrict__ part, int G, int K, double *__restrict__ out,
-                                                             double *__restrict__ sspart, const int *__restrict__ stop) {
+__device__ __forceinline__ void miss_col_finish_body(const double *__restrict__ part, int G, int K, double *__restrict__ out,
+                                                     double *__restrict__ sspart, const int *__restrict__ stop) {
     __shared__ double smem[WG / WAVE];
     if (stop && *stop) return;
     const i64 k = (i64)blockIdx.x * WG + threadIdx.x;
@@ -134,10 +142,14 @@ __global__ __launch_bounds__(WG) void miss_col_finish_kernel(const double *__res
         if (threadIdx.x == 0) sspart[blockIdx.x] = s;
     }
 }
+__global__ __launch_bounds__(WG) void miss_col_finish_kernel(const double *__restrict__ part, int G, int K, double *__restrict__ out,
+                                                             double *__restrict__ sspart, const int *__restrict__ stop) {
+    miss_col_finish_body(part, G, K, out, sspart, stop);
+}
 
 // w <- w / |w|_2, the nb block sums of squares added in a fixed order by every workgroup (|w| = 0: w stays 0)
-__global__ __launch_bounds__(WG) void miss_normalize_kernel(double *__restrict__ w, int K, const double *__restrict__ sspart, int nb,
-                                                            const int *__restrict__ stop) {
+__device__ __forceinline__ void miss_normalize_body(double *__restrict__ w, int K, const double *__restrict__ sspart, int nb,
+                                                    const int *__restrict__ stop) {
     __shared__ double smem[WG / WAVE];
     if (stop && *stop) return;
     double s = 0.0;
@@ -145,6 +157,10 @@ __global__ __launch_bounds__(WG) void miss_normalize_kernel(double *__restrict__
     const double nrm = sqrt(block_sum<WG / WAVE>(s, smem));
     const i64 k = (i64)blockIdx.x * WG + threadIdx.x;
     if (k < K) w[k] = miss_quot(w[k], nrm);
+}
+__global__ __launch_bounds__(WG) void miss_normalize_kernel(double *__restrict__ w, int K, const double *__restrict__ sspart, int nb,
+                                                            const int *__restrict__ stop) {
+    miss_normalize_body(w, K, sspart, nb, stop);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -155,9 +171,9 @@ __global__ __launch_bounds__(WG) void miss_normalize_kernel(double *__restrict__
 //   else                            tpart[blockIdx.y][i] = {num, den}; miss_row_finish_kernel adds the ranges in order
 // ------------------------------------------------------------------------------------------------------------------------------
 template <typename T, int V>
-__global__ __launch_bounds__(WG) void miss_row_kernel(const T *__restrict__ X, i64 ldx, i64 N, int K, const double *__restrict__ w, int lrl,
-                                                      int kper, double *__restrict__ t, double *__restrict__ tpart,
-                                                      const int *__restrict__ stop) {
+__device__ __forceinline__ void miss_row_body(const T *__restrict__ X, i64 ldx, i64 N, int K, const double *__restrict__ w, int lrl,
+                                              int kper, double *__restrict__ t, double *__restrict__ tpart,
+                                              const int *__restrict__ stop) {
     __shared__ double sm[WG][2 * V];
     if (stop && *stop) return;
     const int RL = 1 << lrl, CL = WG >> lrl;
@@ -232,12 +248,18 @@ __global__ __launch_bounds__(WG) void miss_row_kernel(const T *__restrict__ X, i
             }
         }
 }
+template <typename T, int V>
+__global__ __launch_bounds__(WG) void miss_row_kernel(const T *__restrict__ X, i64 ldx, i64 N, int K, const double *__restrict__ w, int lrl,
+                                                      int kper, double *__restrict__ t, double *__restrict__ tpart,
+                                                      const int *__restrict__ stop) {
+    miss_row_body<T, V>(X, ldx, N, K, w, lrl, kper, t, tpart, stop);
+}
 
 // t[i] = num / den over the S ranges.  A workgroup owns MISS_RF_ROWS rows; range lane sl adds the ranges sl, sl + SL, ... in order
 // (SL = WG / MISS_RF_ROWS, four loads in flight), then the SL lanes of a row meet in LDS in the order of sl.
 constexpr int MISS_RF_ROWS = 16;
-__global__ __launch_bounds__(WG) void miss_row_finish_kernel(const double *__restrict__ tpart, int S, i64 N, double *__restrict__ t,
-                                                             const int *__restrict__ stop) {
+__device__ __forceinline__ void miss_row_finish_body(const double *__restrict__ tpart, int S, i64 N, double *__restrict__ t,
+                                                     const int *__restrict__ stop) {
     constexpr int RR = MISS_RF_ROWS, SL = WG / RR;
     __shared__ double sm[SL][RR][2];
     if (stop && *stop) return;
@@ -263,6 +285,10 @@ __global__ __launch_bounds__(WG) void miss_row_finish_kernel(const double *__res
         den += sm[q][ri][1];
     }
     t[i] = miss_quot(num, den);
+}
+__global__ __launch_bounds__(WG) void miss_row_finish_kernel(const double *__restrict__ tpart, int S, i64 N, double *__restrict__ t,
+                                                             const int *__restrict__ stop) {
+    miss_row_finish_body(tpart, S, N, t, stop);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -307,8 +333,8 @@ __global__ __launch_bounds__(WG) void miss_y_deflate_kernel(double *__restrict__
 }
 
 // One wave: the column of Ya with the largest sum of squares (lowest index on ties) -> *jstar; clears the convergence word
-__global__ __launch_bounds__(WAVE) void miss_u_pick_kernel(const double *__restrict__ sspart, int G, int M, int *__restrict__ jstar,
-                                                           int *__restrict__ stop) {
+__device__ __forceinline__ void miss_u_pick_body(const double *__restrict__ sspart, int G, int M, int *__restrict__ jstar,
+                                                 int *__restrict__ stop) {
     __shared__ double ss[MISS_MAX_M];
     for (int j = 0; j < M; ++j) {
         double s = 0.0;
@@ -325,6 +351,10 @@ __global__ __launch_bounds__(WAVE) void miss_u_pick_kernel(const double *__restr
         *stop = 0;
     }
 }
+__global__ __launch_bounds__(WAVE) void miss_u_pick_kernel(const double *__restrict__ sspart, int G, int M, int *__restrict__ jstar,
+                                                           int *__restrict__ stop) {
+    miss_u_pick_body(sspart, G, M, jstar, stop);
+}
 
 __global__ __launch_bounds__(WG) void miss_u_copy_kernel(const double *__restrict__ Ya, i64 N, const int *__restrict__ jstar,
                                                          double *__restrict__ u) {
@@ -333,8 +363,8 @@ __global__ __launch_bounds__(WG) void miss_u_copy_kernel(const double *__restric
 }
 
 // part[blockIdx.x] = {Ya^T t (M), t^T t, |t - tprev|^2} of this workgroup's rows; tprev <- t
-__global__ __launch_bounds__(WG) void miss_yt_kernel(const double *__restrict__ Ya, i64 N, int M, const double *__restrict__ t,
-                                                     double *__restrict__ tprev, double *__restrict__ part, const int *__restrict__ stop) {
+__device__ __forceinline__ void miss_yt_body(const double *__restrict__ Ya, i64 N, int M, const double *__restrict__ t,
+                                             double *__restrict__ tprev, double *__restrict__ part, const int *__restrict__ stop) {
     __shared__ double smem[WG / WAVE];
     if (stop && *stop) return;
     const i64 i_first = (i64)blockIdx.x * WG + threadIdx.x, step = (i64)gridDim.x * WG;
@@ -359,12 +389,16 @@ __global__ __launch_bounds__(WG) void miss_yt_kernel(const double *__restrict__ 
         out[M + 1] = dd;
     }
 }
+__global__ __launch_bounds__(WG) void miss_yt_kernel(const double *__restrict__ Ya, i64 N, int M, const double *__restrict__ t,
+                                                     double *__restrict__ tprev, double *__restrict__ part, const int *__restrict__ stop) {
+    miss_yt_body(Ya, N, M, t, tprev, part, stop);
+}
 
 // One wave: q = Ya^T t / t^T t -> q (a column of Q), *qq = q^T q; the end of iteration `it` of a component: done when there is one
 // response, when it >= 2 and |t - tprev|^2 <= 1e-20 t^T t, or at max_it -- then the convergence word is set and *iters = it
-__global__ __launch_bounds__(WAVE) void miss_q_kernel(const double *__restrict__ part, int G, int M, int it, int max_it,
-                                                      double *__restrict__ q, double *__restrict__ qq, int *__restrict__ stop,
-                                                      long long *__restrict__ iters) {
+__device__ __forceinline__ void miss_q_body(const double *__restrict__ part, int G, int M, int it, int max_it,
+                                            double *__restrict__ q, double *__restrict__ qq, int *__restrict__ stop,
+                                            long long *__restrict__ iters) {
     __shared__ double val[MISS_MAX_M + 2];
     if (stop && *stop) return;
     for (int v = 0; v < M + 2; ++v) {  // the lanes share the G partial rows of a value, then the butterfly: a fixed order
@@ -389,6 +423,11 @@ __global__ __launch_bounds__(WAVE) void miss_q_kernel(const double *__restrict__
             if (iters) *iters = it;
         }
     }
+}
+__global__ __launch_bounds__(WAVE) void miss_q_kernel(const double *__restrict__ part, int G, int M, int it, int max_it,
+                                                      double *__restrict__ q, double *__restrict__ qq, int *__restrict__ stop,
+                                                      long long *__restrict__ iters) {
+    miss_q_body(part, G, M, it, max_it, q, qq, stop, iters);
 }
 
 // u = Ya q / q^T q

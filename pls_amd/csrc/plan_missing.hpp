@@ -8,43 +8,11 @@ namespace {
 
 constexpr int MISS_BATCH = 8;  // iterations of the M > 1 loop enqueued between two reads of the convergence word
 
-// geometry of the three sweeps of one call; the work copy has 16-byte columns (ldw a multiple of 16 / sizeof(T))
-struct MissGeom {
-    i64 ldw;
-    int G;        // row groups (partial rows) of the column sweep
-    i64 nkg;      // its column groups
-    int lrl;      // row sweep: log2 of the row lanes of a workgroup
-    i64 nrb;      //            row blocks
-    int S, kper;  //            K ranges (1: no partials) and the columns of one
-    int GY;       // workgroups of the row-chunked kernels of the Y side
-    i64 nbK, nbN;  // blocks of the K- and N-parallel kernels
-};
-
+// geometry of the three sweeps of one call: miss_layout.hpp, a pure function of (N, K, type, CU count)
+using plsk::MissGeom;
 template <typename T>
 MissGeom miss_geom(const pls_hip_context *c, i64 N, int K) {
-    constexpr int FV = 16 / (int)sizeof(T);
-    MissGeom g;
-    g.ldw = N + ((-N) & (FV - 1));
-    g.nkg = ((i64)K + plsk::MISS_KC - 1) / plsk::MISS_KC;
-    // the worst case of the row chunks (a caller's matrix that is not 16-byte aligned is walked one row per lane)
-    const i64 nch = (N + plsk::WG - 1) / plsk::WG;
-    // 5 workgroups per CU are resident at the 89 VGPRs of the deflating sweep: all of them in one round, no tail
-    g.G = (int)std::min<i64>(std::min<i64>(std::max<i64>(1, (5 * (i64)c->num_cu) / g.nkg), nch), 65535);
-    const i64 nv = (N + FV - 1) / FV;
-    g.lrl = 0;
-    while ((1 << g.lrl) < plsk::WG && ((i64)1 << g.lrl) < nv) ++g.lrl;
-    const int RL = 1 << g.lrl, CL = plsk::WG >> g.lrl;
-    g.nrb = (nv + RL - 1) / RL;
-    const i64 smax = std::max<i64>(1, (i64)K / (8 * CL));  // at least 8 columns per lane of a range
-    i64 S = std::min<i64>(std::min<i64>(std::max<i64>(1, (4 * (i64)c->num_cu) / g.nrb), smax), 65535);
-    i64 kper = ((i64)K + S - 1) / S;
-    kper += (-kper) & (CL - 1);
-    g.kper = (int)std::min<i64>(kper, ((i64)1 << 31) - 1);
-    g.S = (int)(((i64)K + g.kper - 1) / g.kper);
-    g.GY = (int)std::min<i64>(nch, 2 * (i64)c->num_cu);
-    g.nbK = ((i64)K + plsk::WG - 1) / plsk::WG;
-    g.nbN = nch;
-    return g;
+    return plsk::miss_geom_of(N, K, (int)sizeof(T), c->num_cu);
 }
 
 // the small workspace of a call, carved from c->mws in doubles

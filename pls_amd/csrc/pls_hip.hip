@@ -41,6 +41,7 @@
 #include "resample_kernels.hpp"
 #include "synth_kernels.hpp"
 #include "missing_kernels.hpp"
+#include "missing_cv_kernels.hpp"
 #include "host_pipeline.hpp"
 #include "exchange_kernels.hpp"
 
@@ -122,6 +123,7 @@ int pls_hip_create(pls_hip_handle *out, int device, void *stream) {
         c->env.dualbatch_sweeps = on("PLS_HIP_DUALBATCH_SWEEPS");
         c->env.cvbatch_refit = on("PLS_HIP_CVBATCH_REFIT");
         if (const char *e = getenv("PLS_HIP_DUALCVB_ROUND")) c->env.dualcvb_round = atoll(e);
+        if (const char *e = getenv("PLS_HIP_MISSCV_ROUND")) c->env.misscv_round = atoll(e);
         c->env.tail = !off("PLS_HIP_TAIL");
         {
             const char *e = getenv("PLS_HIP_TAIL");
@@ -566,6 +568,7 @@ int pls_hip_sse_by_components(pls_hip_handle h, const void *S, int64_t lds, cons
 #include "plan_resample.hpp"
 #include "plan_dual_cvbatch.hpp"
 #include "plan_missing.hpp"
+#include "plan_missing_cv.hpp"
 
 
 extern "C" {
@@ -877,6 +880,64 @@ int pls_hip_fit_missing(pls_hip_handle h, const void *X, int64_t ldx, const void
         if (B) CHK(d2h(h, B, K, dB, K, K, M, 8));
         CHK(d2h(h, T, ldt, dT, dldt, N, A, es));
         if (iters) CHK(d2h(h, iters, A, dit, A, A, 1, 8));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return PLS_HIP_OK;
+}
+
+int pls_hip_cv_folds_missing(pls_hip_handle h, const void *X, int64_t ldx, const void *Y, int64_t ldy, int64_t N, int64_t K, int64_t M,
+                             int64_t A, const int64_t *test_idx, int64_t test_size, int64_t num_folds, int dtype, int mem, double *E,
+                             int64_t *iters) {
+    CHK(check_handle(h));
+    if (dtype != PLS_HIP_F64 && dtype != PLS_HIP_F32) return fail(h, PLS_HIP_ERR_INVALID, "bad dtype");
+    if (mem != PLS_HIP_MEM_HOST && mem != PLS_HIP_MEM_DEVICE) return fail(h, PLS_HIP_ERR_INVALID, "bad mem kind");
+    if (N < 2 || K < 1 || M < 1 || A < 1 || A > K || !X || !Y || !test_idx || !E || test_size < 1 || test_size >= N || num_folds < 1 ||
+        ldx < N || ldy < N || num_folds > (1 << 22) || test_size > (1 << 20))
+        return fail(h, PLS_HIP_ERR_INVALID, "bad cv_folds_missing arguments: need N>=2, 1<=A<=K, M>=1, ld>=N, 1<=test_size<N, X, Y, test_idx and E");
+    if (K > (((i64)1 << 31) - 1) || M > plsk::MISS_MAX_M)
+        return fail(h, PLS_HIP_ERR_UNSUPPORTED, "cv_folds_missing takes at most 32 responses (and K < 2^31)");
+    if (h->reducer || h->nranks > 1)
+        return fail(h, PLS_HIP_ERR_UNSUPPORTED, "cv_folds_missing needs every row of X on one handle: not on a row-sharded handle");
+    const i64 nobs = num_folds * test_size;
+    {
+        std::unique_ptr<i64[]> fold_of(new (std::nothrow) i64[(size_t)N]);  // the last fold that held a row out
+        if (!fold_of) return fail(h, PLS_HIP_ERR_ALLOC, "cv_folds_missing: no host memory for the index check");
+        std::fill_n(fold_of.get(), N, (i64)-1);
+        for (i64 f = 0; f < num_folds; ++f)
+            for (i64 j = f * test_size; j < (f + 1) * test_size; ++j) {
+                if (test_idx[j] < 0 || test_idx[j] >= N) return fail(h, PLS_HIP_ERR_INVALID, "cv_folds_missing: test index out of range");
+                if (fold_of[test_idx[j]] == f) return fail(h, PLS_HIP_ERR_INVALID, "cv_folds_missing: a fold holds a row out twice");
+                fold_of[test_idx[j]] = f;
+            }
+    }
+    CHK(set_device(h));
+    const size_t es = esize(dtype);
+    const void *dX = X, *dY = Y;
+    double *dE = E;
+    long long *dit = (long long *)iters;
+    i64 dldx = ldx, dldy = ldy;
+    if (mem == PLS_HIP_MEM_HOST) {
+        const i64 ldn = N + ((-N) & 3);  // 16-byte columns for either type
+        CHK(ensure(h, h->hX, (size_t)ldn * K * es));
+        CHK(ensure(h, h->hY, (size_t)ldn * M * es));
+        CHK(ensure(h, h->cve, (size_t)nobs * A * M * 8));
+        if (iters) CHK(ensure(h, h->mit, (size_t)num_folds * A * 8));
+        CHK(h2d(h, h->hX.p, ldn, X, ldx, N, K, es));
+        CHK(h2d(h, h->hY.p, ldn, Y, ldy, N, M, es));
+        dX = h->hX.p; dY = h->hY.p; dE = (double *)h->cve.p;
+        dit = iters ? (long long *)h->mit.p : nullptr;
+        dldx = dldy = ldn;
+    }
+    CHK(ensure(h, h->mcvidx, (size_t)nobs * 8));
+    HIPCHK(h, hipMemcpyAsync(h->mcvidx.p, test_idx, (size_t)nobs * 8, hipMemcpyHostToDevice, h->stream));
+    CHK(by_dtype(dtype, [&](auto t) {
+        using Tx = decltype(t);
+        return cv_folds_missing_device<Tx>(h, (const Tx *)dX, dldx, (const Tx *)dY, dldy, N, (int)K, (int)M, (int)A,
+                                           (const long long *)h->mcvidx.p, (int)test_size, num_folds, dE, dit);
+    }));
+    if (mem == PLS_HIP_MEM_HOST) {
+        HIPCHK(h, hipMemcpyAsync(E, dE, (size_t)nobs * A * M * 8, hipMemcpyDeviceToHost, h->stream));
+        if (iters) HIPCHK(h, hipMemcpyAsync(iters, dit, (size_t)num_folds * A * 8, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     return PLS_HIP_OK;

@@ -689,6 +689,41 @@ class Handle:
         full = dict(W=W, P=P, Q=Q, R=R, T=T, B=B, iters=iters)
         return {k: full[k] for k in _MISSING_OUT if k in want}
 
+    def cv_folds_missing(self, X, Y, A: int, test_idx, want_iters: bool = False):
+        """Residuals of cross-validation folds of X whose NaN cells are missing values (pls_hip_cv_folds_missing): fold f is
+        fit_missing on all rows but test_idx[f], scores_missing on the held-out rows, E_c = Y_test - S[:, :c] Q[:, :c]^T.
+        test_idx: (num_folds, test_size).  Returns E with shape (M, nobs, A) as cv_folds does -- validation takes it unchanged --
+        or (E, iters) with iters (num_folds, A) int64 when want_iters.  All folds of a round run in the same launches; the
+        bits of a fold do not depend on the other folds.  M <= 32; a handle with a reducer: PLS_HIP_ERR_UNSUPPORTED."""
+        idx = np.ascontiguousarray(np.asarray(test_idx, dtype=np.int64))
+        if idx.ndim == 1:
+            idx = idx[:, None]
+        nf, ts = idx.shape
+        if _is_torch(X):
+            X = as_colmajor(X); Y = as_colmajor(Y, X.dtype)
+            N, K = X.shape
+            M = Y.shape[1]
+            E = torch.empty((M, A, nf * ts), dtype=torch.float64, device=X.device)
+            iters = torch.empty((nf, A), dtype=torch.int64, device=X.device) if want_iters else None
+            rc = self._lib.pls_hip_cv_folds_missing(self.h, X.data_ptr() or None, _ld(X), Y.data_ptr() or None, _ld(Y), N, K, M, A,
+                                                    idx.ctypes.data_as(ctypes.c_void_p), ts, nf, self._dt(X), L.MEM_DEVICE,
+                                                    E.data_ptr(), iters.data_ptr() if want_iters else None)
+            L.check(rc, self.h)
+            E = E.permute(0, 2, 1)
+        else:
+            dt = np.float32 if np.asarray(X).dtype == np.float32 else np.float64
+            X = _np_f(X, dt); Y = _np_f(Y, dt)
+            N, K = X.shape
+            M = Y.shape[1]
+            E = np.zeros((M, A, nf * ts))
+            iters = np.zeros((nf, A), dtype=np.int64) if want_iters else None
+            p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
+            rc = self._lib.pls_hip_cv_folds_missing(self.h, p(X), max(N, 1), p(Y), max(N, 1), N, K, M, A, p(idx), ts, nf,
+                                                    L.F64 if dt == np.float64 else L.F32, L.MEM_HOST, p(E), p(iters))
+            L.check(rc, self.h)
+            E = E.transpose(0, 2, 1)
+        return (E, iters) if want_iters else E
+
     def scores_missing(self, X, W, P):
         """Scores of rows, new or training, that may have missing cells (pls_hip_scores_missing): sequential deflation with
         the model's W and P (K, A).  (N, A) in the dtype of X.  On complete rows it equals xb(X, R)."""
@@ -1046,6 +1081,7 @@ class Model:
         self.method = algorithm
         self.W = self.P = self.R = self.Q = self.T = None
         self._X, self._Y = X, Y  # the reference keeps _X, _Y for its cross-validation methods (pls.h:250)
+        self._missing = False  # plsr_missing sets it: cross-validation then treats NaN in X as missing cells too
         if missing:  # NaN in X marks a missing cell (plsr_missing)
             self.plsr_missing(X, Y)
         else:
@@ -1054,6 +1090,7 @@ class Model:
     # void plsr(const Mat2D&, const Mat2D&, const METHOD&)  include/PLS/pls.h:199
     def plsr(self, X, Y, algorithm: int = KERNEL_TYPE1):
         self.method = algorithm
+        self._missing = False
         if _is_torch(X):
             out = self.handle.fit_device(X, Y, self.A, algorithm, want_B=False)
         else:
@@ -1067,6 +1104,7 @@ class Model:
         plsr fills, so scores, coefficients, fitted_values and loadingsX/Y work unchanged on complete new data; rows with
         missing cells go through scores_missing / fitted_values_missing.  Model(X, Y, missing=True) fits this way."""
         self.method = KERNEL_TYPE1
+        self._missing = True
         out = self.handle.fit_missing(X, Y, self.A, want=("W", "P", "Q", "R", "T", "iters"))
         self.W, self.P, self.Q, self.R, self.T = (out[k] for k in "WPQRT")
         self.iters = out["iters"]
@@ -1128,7 +1166,7 @@ class Model:
         """leave-one-out: fold i refits on all rows but i (all folds in one batched device call).  The handle's plan decides
         the route (Handle.cv_folds): under ALGO_DUAL every fold runs from one X X^T."""
         n = self._X.shape[0]
-        return self.handle.cv_folds(self._X, self._Y, self.A, np.arange(n)[:, None])
+        return self._cv_folds(self._X, self._Y, self.A, np.arange(n)[:, None])
 
     def cv_LSO(self, test_fraction: float, num_trials: int, rng=None):
         """leave-some-out: num_trials random splits with round(test_fraction*N) held-out rows each.
@@ -1141,11 +1179,16 @@ class Model:
             raise L.PlsHipError(L.ERR_INVALID, "empty train or test split")
         rng = np.random.default_rng() if rng is None else rng
         idx = np.stack([rng.permutation(n)[:ts] for _ in range(num_trials)])
-        return self.handle.cv_folds(self._X, self._Y, self.A, idx)
+        return self._cv_folds(self._X, self._Y, self.A, idx)
+
+    def _cv_folds(self, X, Y, A, idx):
+        """a model fitted with missing=True / plsr_missing cross-validates with the missing cells skipped (Handle.cv_folds_missing)"""
+        return (self.handle.cv_folds_missing if self._missing else self.handle.cv_folds)(X, Y, A, idx)
 
     def cv_NEW_DATA(self, X_new, Y_new):
-        """residuals on data outside the fit for 1..A components (src/pls.cpp:494-509); no refit"""
-        S = self.scores(X_new)
+        """residuals on data outside the fit for 1..A components (src/pls.cpp:494-509); no refit.  A model fitted with
+        missing=True / plsr_missing takes the scores from scores_missing: X_new may have missing cells"""
+        S = self.scores_missing(X_new) if self._missing else self.scores(X_new)
         if _is_torch(S):
             Y2 = (Y_new if Y_new.dim() == 2 else Y_new[:, None]).to(torch.float64)
             fit = torch.cumsum(S.to(torch.float64)[:, :, None] * self.Q.t()[None, :, :], dim=1)  # (N, A, M)
