@@ -130,7 +130,36 @@ struct pls_hip_context {
         int tail_update = 1;  // 0: never, 1: in the tail of READ-ONLY passes (default), 2: of every pass
         int xb4 = 1;          // PLS_HIP_XB4=0: X B with 5..32 columns on the older kernels
         int resident_gram = 1;  // PLS_HIP_RESIDENT_GRAM=0: AUTO's mid-size fits on the per-component resident kernels; 2: also under KERNEL (measurements); 4: the row form of its first phase everywhere
-    } env;
+    };
+    static void read_env(Env &env) {  // (pls_hip_create)
+        auto off = [](const char *name) { const char *e = getenv(name); return e && atoi(e) == 0; };
+        auto on = [](const char *name) { const char *e = getenv(name); return e && atoi(e) != 0; };
+        auto num = [](const char *name, i64 &v) { if (const char *e = getenv(name)) v = atoll(e); };
+        env.tiny = !off("PLS_HIP_TINY");
+        env.cv_refit = on("PLS_HIP_CV_REFIT");
+        env.batch_refit = on("PLS_HIP_BATCH_REFIT");
+        num("PLS_HIP_BATCH_ROUND", env.batch_round);
+        num("PLS_HIP_DUALCV_ROUND", env.dualcv_round);
+        num("PLS_HIP_DUALBATCH_ROUND", env.dualbatch_round);
+        num("PLS_HIP_RESAMPLE_ROUND", env.resample_round);
+        env.resample_refit = on("PLS_HIP_RESAMPLE_REFIT");
+        env.dualbatch_sweeps = on("PLS_HIP_DUALBATCH_SWEEPS");
+        env.cvbatch_refit = on("PLS_HIP_CVBATCH_REFIT");
+        num("PLS_HIP_DUALCVB_ROUND", env.dualcvb_round);
+        num("PLS_HIP_MISSCV_ROUND", env.misscv_round);
+        env.tail = !off("PLS_HIP_TAIL");
+        const char *tail = getenv("PLS_HIP_TAIL");
+        env.tail_update = tail ? (atoi(tail) >= 2 ? 2 : 0) : 1;
+        env.replica_guard = !off("PLS_HIP_REPLICA_GUARD");
+        env.resident = !off("PLS_HIP_RESIDENT");
+        env.turnaround = !off("PLS_HIP_TURNAROUND");
+#ifdef PLS_HIP_TESTING
+        num("PLS_HIP_TEST_TURN_EDGE_BYTES", env.turn_edge_bytes);  // (small matrices with a bulk, tests only)
+#endif
+        if (const char *e = getenv("PLS_HIP_XB4")) env.xb4 = atoi(e);
+        if (const char *e = getenv("PLS_HIP_RESIDENT_GRAM")) env.resident_gram = atoi(e);
+    }
+    Env env;
     // replica guard of sharded fits (small_kernels.hpp): host-mapped flag "the ranks derived different W/P/Q/R/B"
     int *diverged = nullptr, *diverged_dev = nullptr;
     DevBuf guard;

@@ -186,21 +186,15 @@ int fit_batch_impl(pls_hip_context *h, const void *X, i64 ldx, const void *Ys, i
     const void *dX = X, *dY = Ys;
     i64 dldx = ldx, dldy = ldy;
     double *dR = R, *dQ = Q, *dtt = tt, *dB = B, *dssy = ssy;
-    HostOutputs outs(h);
-    if (mem == PLS_HIP_MEM_HOST) {
-        const i64 n1 = std::max<i64>(N, 1), ldn = n1 + ((-n1) & 3);  // 16-byte columns for either type
-        CHK(ensure(h, h->hX, (size_t)ldn * K * es));
-        CHK(ensure(h, h->bY, (size_t)ldn * C * es));
-        CHK(outs.out(dR, R, h->boR, nprob * K * A, 0, K * A, nprob));
-        CHK(outs.out(dQ, Q, h->boQ, nprob * M * A, 0, M * A, nprob));
-        CHK(outs.out(dtt, tt, h->bott, nprob * A, 0, A, nprob));
-        CHK(outs.out(dB, B, h->boB, nprob * K * M, 0, K * M, nprob));
-        CHK(outs.out(dssy, ssy, h->bossy, nprob * M, 0, M, nprob));
-        CHK(h2d(h, h->hX.p, ldn, X, ldx, N, K, es));
-        CHK(h2d(h, h->bY.p, ldn, Ys, ldy, N, C, es));
-        dX = h->hX.p; dY = h->bY.p;
-        dldx = dldy = ldn;
-    }
+    const i64 ldn = ld_quad(N);
+    HostCall hc(h, mem);
+    CHK(hc.out(dR, R, h->boR, K * A, nprob));
+    CHK(hc.out(dQ, Q, h->boQ, M * A, nprob));
+    CHK(hc.out(dtt, tt, h->bott, A, nprob));
+    CHK(hc.out(dB, B, h->boB, K * M, nprob));
+    CHK(hc.out(dssy, ssy, h->bossy, M, nprob));
+    CHK(hc.in(dX, dldx, X, ldx, h->hX, N, K, es, ldn));
+    CHK(hc.in(dY, dldy, Ys, ldy, h->bY, N, C, es, ldn));
     int rc = PLS_HIP_ERR_ALLOC;
     if (batch_dual_covers(h, N, M)) {  // the sample-space plan, an explicit opt-in: every problem from one X X^T
         rc = by_dtype(dtype, [&](auto t) {
@@ -227,12 +221,7 @@ int fit_batch_impl(pls_hip_context *h, const void *X, i64 ldx, const void *Ys, i
         });
     }
     if (rc != PLS_HIP_OK) return rc;
-    if (mem == PLS_HIP_MEM_HOST) {
-        CHK(outs.copy_back());
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        CHK(check_diverged(h));
-    }
-    return PLS_HIP_OK;
+    return hc.finish(true);
 }
 
 }  // namespace

@@ -313,20 +313,16 @@ int cv_folds_sharded(pls_hip_context *h, const void *X, i64 ldx, const void *Y, 
     const i64 fchunk = std::max<i64>(1, std::min<i64>(num_folds, CV_MSG_CAP / (ts * (K + M))));
     const i64 echunk = batched ? std::min<i64>(CV_MSG_CAP, nobs * A * M) : 0;
     const void *dX = X, *dY = Y;
+    double *dE = E;
     i64 dldx = ldx, dldy = ldy;
+    HostCall hc(h, mem);
     // Phase 1, local: stage host data and size every workspace of the call.  A failure is carried by the partition message,
     // so that no rank is left waiting in a collective its peers never reach.
     const int local = [&]() -> int {
-        if (mem == PLS_HIP_MEM_HOST) {
-            const i64 n1 = std::max<i64>(N, 1), ldn = n1 + ((-n1) & 3);
-            CHK(ensure(h, h->hX, (size_t)ldn * K * es));
-            CHK(ensure(h, h->hY, (size_t)ldn * M * es));
-            CHK(h2d(h, h->hX.p, ldn, X, ldx, N, K, es));
-            CHK(h2d(h, h->hY.p, ldn, Y, ldy, N, M, es));
-            dX = h->hX.p; dY = h->hY.p;
-            dldx = dldy = ldn;
-            CHK(ensure(h, h->cve, (size_t)nobs * A * M * 8));
-        }
+        const i64 ldn = ld_quad(N);
+        CHK(hc.in(dX, dldx, X, ldx, h->hX, N, K, es, ldn));
+        CHK(hc.in(dY, dldy, Y, ldy, h->hY, N, M, es, ldn));
+        CHK(hc.out_flat(dE, E, h->cve, (size_t)nobs * A * M * 8));
         CHK(ensure(h, h->cvidx, (size_t)nobs * 8));
         CHK(ensure(h, h->cvx, (size_t)nobs * K * 8));
         CHK(ensure(h, h->cvy, (size_t)nobs * M * 8));
@@ -358,9 +354,7 @@ int cv_folds_sharded(pls_hip_context *h, const void *X, i64 ldx, const void *Y, 
     if (n_total < 2) return fail(h, PLS_HIP_ERR_INVALID, "bad cv_folds arguments: fewer than 2 rows over all ranks");
     if (ts >= n_total)
         return fail(h, PLS_HIP_ERR_INVALID, "cv_folds: test_size >= n_total -- a fold would leave no training rows");
-    for (i64 j = 0; j < nobs; ++j)
-        if (test_idx[j] < 0 || test_idx[j] >= n_total) return fail(h, PLS_HIP_ERR_INVALID, "cv_folds: test index out of range");
-    double *dE = (mem == PLS_HIP_MEM_HOST) ? (double *)h->cve.p : E;
+    CHK(check_test_idx(h, test_idx, nobs, n_total, "cv_folds"));
     HIPCHK(h, hipMemcpyAsync(h->cvidx.p, test_idx, (size_t)nobs * 8, hipMemcpyHostToDevice, h->stream));
     const int Ki = (int)K, Mi = (int)M, Ai = (int)A, tsi = (int)ts;
     const int rc = by_dtype(dtype, [&](auto t) {
@@ -372,10 +366,7 @@ int cv_folds_sharded(pls_hip_context *h, const void *X, i64 ldx, const void *Y, 
                                          dE);
     });
     if (rc != PLS_HIP_OK) return rc;
-    if (mem == PLS_HIP_MEM_HOST)
-        HIPCHK(h, hipMemcpyAsync(E, dE, (size_t)nobs * A * M * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return check_diverged(h);  // (the replica guard of the refit route's fits; a timed-out device-side exchange)
+    return hc.finish(true, true);  // (the replica guard of the refit route's fits; a timed-out device-side exchange)
 }
 
 }  // namespace

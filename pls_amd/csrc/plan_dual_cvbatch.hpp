@@ -109,23 +109,18 @@ int cv_press_batch_refit(pls_hip_context *c, const T *X, i64 ldx, const T *Ys, i
 int cv_press_batch_impl(pls_hip_context *h, const void *X, i64 ldx, const void *Ys, i64 ldy, i64 N, i64 K, i64 M, i64 A, i64 nprob,
                         const int64_t *test_idx, i64 ts, i64 num_folds, int dtype, int mem, double *PRESS, double *ssy, double *E) {
     const size_t es = esize(dtype);
-    const i64 nobs = num_folds * ts, MA = M * A, C = nprob * M, ne = M * nobs * A;
+    const i64 nobs = num_folds * ts, MA = M * A, C = nprob * M;
     const void *dX = X, *dY = Ys;
     i64 dldx = ldx, dldy = ldy;
     double *dP = PRESS, *dS = ssy, *dE = E;
-    HostOutputs outs(h);
-    if (mem == PLS_HIP_MEM_HOST) {
-        const i64 ldn = N + ((-N) & 3);  // 16-byte columns for either type
-        CHK(ensure(h, h->hX, (size_t)ldn * K * es));
-        CHK(ensure(h, h->bY, (size_t)ldn * C * es));
-        CHK(outs.out(dP, PRESS, h->cvbo, nprob * (MA + M), 0, MA, nprob));  // cvbo = [PRESS | ssy]
-        CHK(outs.out(dS, ssy, h->cvbo, nprob * (MA + M), nprob * MA, M, nprob));
-        CHK(outs.out(dE, E, h->cvboE, nprob * ne, 0, nobs, nprob * MA));
-        CHK(h2d(h, h->hX.p, ldn, X, ldx, N, K, es));
-        CHK(h2d(h, h->bY.p, ldn, Ys, ldy, N, C, es));
-        dX = h->hX.p; dY = h->bY.p;
-        dldx = dldy = ldn;
-    }
+    const i64 ldn = ld_quad(N);
+    const size_t sums = (size_t)nprob * (MA + M) * 8;  // cvbo = [PRESS | ssy]
+    HostCall hc(h, mem);
+    CHK(hc.out(dP, PRESS, h->cvbo, MA, nprob, 8, sums, 0));
+    CHK(hc.out(dS, ssy, h->cvbo, M, nprob, 8, sums, (size_t)nprob * MA * 8));
+    CHK(hc.out(dE, E, h->cvboE, nobs, nprob * MA));
+    CHK(hc.in(dX, dldx, X, ldx, h->hX, N, K, es, ldn));
+    CHK(hc.in(dY, dldy, Ys, ldy, h->bY, N, C, es, ldn));
     int rc = PLS_HIP_ERR_ALLOC;
     if (cvbatch_dual_covers(h, N, M)) {  // the sample-space plan, an explicit opt-in: every problem and fold from one X X^T
         rc = by_dtype(dtype, [&](auto t) {
@@ -142,10 +137,8 @@ int cv_press_batch_impl(pls_hip_context *h, const void *X, i64 ldx, const void *
                                            dP, dS, dE);
         });
     if (rc != PLS_HIP_OK) return rc;
-    if (mem == PLS_HIP_MEM_HOST) CHK(outs.copy_back());
-    // the index list is host memory of the caller, and the call returns after the work has completed
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return PLS_HIP_OK;
+    // the index list is host memory of the caller, and the call returns after the work has completed, whatever `mem` is
+    return hc.finish(false, true);
 }
 
 }  // namespace

@@ -182,25 +182,18 @@ int fit_resampled_impl(pls_hip_context *h, const void *X, i64 ldx, const void *Y
     const double *dW = Wt;
     i64 dldx = ldx, dldy = ldy, dldw = ldw;
     double *dQ = Q, *dtt = tt, *dB = B, *dB0 = B0, *dBmean = Bmean, *dBm2 = Bm2;
-    HostOutputs outs(h);
-    if (mem == PLS_HIP_MEM_HOST) {
-        const i64 ldn = N + ((-N) & 3);  // 16-byte columns for either type
-        CHK(ensure(h, h->hX, (size_t)ldn * K * es));
-        CHK(ensure(h, h->hY, (size_t)ldn * M * es));
-        CHK(ensure(h, h->rsW, (size_t)N * nrep * 8));
-        CHK(outs.out(dQ, Q, h->boQ, nrep * M * A, 0, M * A, nrep));
-        CHK(outs.out(dtt, tt, h->bott, nrep * A, 0, A, nrep));
-        CHK(outs.out(dB, B, h->boB, nrep * KM, 0, KM, nrep));
-        CHK(outs.out(dB0, B0, h->rsoS, 3 * KM, 0, KM, 1));  // rsoS = [B0 | Bmean | Bm2]
-        CHK(outs.out(dBmean, Bmean, h->rsoS, 3 * KM, KM, KM, 1));
-        CHK(outs.out(dBm2, Bm2, h->rsoS, 3 * KM, 2 * KM, KM, 1));
-        CHK(h2d(h, h->hX.p, ldn, X, ldx, N, K, es));
-        CHK(h2d(h, h->hY.p, ldn, Y, ldy, N, M, es));
-        CHK(h2d(h, h->rsW.p, N, Wt, ldw, N, nrep, 8));
-        dX = h->hX.p; dY = h->hY.p; dW = (const double *)h->rsW.p;
-        dldx = dldy = ldn;
-        dldw = N;
-    }
+    const i64 ldn = ld_quad(N);
+    const size_t summary = (size_t)3 * KM * 8;  // rsoS = [B0 | Bmean | Bm2]
+    HostCall hc(h, mem);
+    CHK(hc.out(dQ, Q, h->boQ, M * A, nrep));
+    CHK(hc.out(dtt, tt, h->bott, A, nrep));
+    CHK(hc.out(dB, B, h->boB, KM, nrep));
+    CHK(hc.out(dB0, B0, h->rsoS, KM, 1, 8, summary, 0));
+    CHK(hc.out(dBmean, Bmean, h->rsoS, KM, 1, 8, summary, (size_t)KM * 8));
+    CHK(hc.out(dBm2, Bm2, h->rsoS, KM, 1, 8, summary, (size_t)2 * KM * 8));
+    CHK(hc.in(dX, dldx, X, ldx, h->hX, N, K, es, ldn));
+    CHK(hc.in(dY, dldy, Y, ldy, h->hY, N, M, es, ldn));
+    CHK(hc.in(dW, dldw, Wt, ldw, h->rsW, N, nrep, 8, ld_exact(N)));
     int rc = PLS_HIP_ERR_ALLOC;
     if (resample_dual_covers(h, N, M)) {  // the sample-space plan, an explicit opt-in: every replicate from one X X^T
         rc = by_dtype(dtype, [&](auto t) {
@@ -217,12 +210,7 @@ int fit_resampled_impl(pls_hip_context *h, const void *X, i64 ldx, const void *Y
                                           dB, dB0, dBmean, dBm2);
         });
     if (rc != PLS_HIP_OK) return rc;
-    if (mem == PLS_HIP_MEM_HOST) {
-        CHK(outs.copy_back());
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        CHK(check_diverged(h));
-    }
-    return PLS_HIP_OK;
+    return hc.finish(true);
 }
 
 }  // namespace

@@ -140,14 +140,12 @@ int validation_impl(pls_hip_context *c, const double *E, i64 nobs, int A, int M,
     }
     CHK(val_press_finish(c, part, nchunk, A, M, dP, dR));
     if (ranks) CHK(val_signed_ranks(c, dE, nobs, A, M, dR, dD, dW));
-    if (!dev) {
-        if (PRESS) HIPCHK(c, hipMemcpyAsync(PRESS, dP, (size_t)MA * 8, hipMemcpyDeviceToHost, c->stream));
-        if (D) HIPCHK(c, hipMemcpyAsync(D, dD, (size_t)MA * 8, hipMemcpyDeviceToHost, c->stream));
-        if (probw) HIPCHK(c, hipMemcpyAsync(probw, dW, (size_t)MA * 8, hipMemcpyDeviceToHost, c->stream));
-        if (ref) HIPCHK(c, hipMemcpyAsync(ref, dR, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    return PLS_HIP_OK;
+    HostCall hc(c, mem);  // (every output has its place in valout already, asked for or not)
+    CHK(hc.back_flat(PRESS, dP, (size_t)MA * 8));
+    CHK(hc.back_flat(D, dD, (size_t)MA * 8));
+    CHK(hc.back_flat(probw, dW, (size_t)MA * 8));
+    CHK(hc.back_flat(ref, dR, (size_t)M * 8));
+    return hc.finish();
 }
 
 }  // namespace

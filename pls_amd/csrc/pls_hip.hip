@@ -56,8 +56,21 @@ using plsk::i64;
 #include "plan_fit_single.hpp"
 #include "plan_fit.hpp"
 #include "host_entry.hpp"
+#include "fit_graph.hpp"
 #include "plan_validation.hpp"
 #include "plan_xdiag.hpp"
+#include "plan_stats.hpp"
+#include "plan_cv.hpp"
+#include "dual_round.hpp"
+#include "plan_dual_cv.hpp"
+#include "plan_dual_batch.hpp"
+#include "plan_batch.hpp"
+#include "plan_resample.hpp"
+#include "plan_dual_cvbatch.hpp"
+#include "plan_missing.hpp"
+#include "plan_missing_cv.hpp"
+#include "xchg_ipc.hpp"
+#include "group_impl.hpp"
 
 // =============================================================================================
 // C-ABI
@@ -109,35 +122,7 @@ int pls_hip_create(pls_hip_handle *out, int device, void *stream) {
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return PLS_HIP_ERR_DEVICE;  // no other target
     pls_hip_context *c = new (std::nothrow) pls_hip_context();
     if (!c) return PLS_HIP_ERR_ALLOC;
-    {
-        auto off = [](const char *name) { const char *e = getenv(name); return e && atoi(e) == 0; };
-        auto on = [](const char *name) { const char *e = getenv(name); return e && atoi(e) != 0; };
-        c->env.tiny = !off("PLS_HIP_TINY");
-        c->env.cv_refit = on("PLS_HIP_CV_REFIT");
-        c->env.batch_refit = on("PLS_HIP_BATCH_REFIT");
-        if (const char *e = getenv("PLS_HIP_BATCH_ROUND")) c->env.batch_round = atoll(e);
-        if (const char *e = getenv("PLS_HIP_DUALCV_ROUND")) c->env.dualcv_round = atoll(e);
-        if (const char *e = getenv("PLS_HIP_DUALBATCH_ROUND")) c->env.dualbatch_round = atoll(e);
-        if (const char *e = getenv("PLS_HIP_RESAMPLE_ROUND")) c->env.resample_round = atoll(e);
-        c->env.resample_refit = on("PLS_HIP_RESAMPLE_REFIT");
-        c->env.dualbatch_sweeps = on("PLS_HIP_DUALBATCH_SWEEPS");
-        c->env.cvbatch_refit = on("PLS_HIP_CVBATCH_REFIT");
-        if (const char *e = getenv("PLS_HIP_DUALCVB_ROUND")) c->env.dualcvb_round = atoll(e);
-        if (const char *e = getenv("PLS_HIP_MISSCV_ROUND")) c->env.misscv_round = atoll(e);
-        c->env.tail = !off("PLS_HIP_TAIL");
-        {
-            const char *e = getenv("PLS_HIP_TAIL");
-            c->env.tail_update = e ? (atoi(e) >= 2 ? 2 : 0) : 1;
-        }
-        c->env.replica_guard = !off("PLS_HIP_REPLICA_GUARD");
-        c->env.resident = !off("PLS_HIP_RESIDENT");
-        c->env.turnaround = !off("PLS_HIP_TURNAROUND");
-#ifdef PLS_HIP_TESTING
-        if (const char *e = getenv("PLS_HIP_TEST_TURN_EDGE_BYTES")) c->env.turn_edge_bytes = atoll(e);  // (small matrices with a bulk, tests only)
-#endif
-        if (const char *e = getenv("PLS_HIP_XB4")) c->env.xb4 = atoi(e);
-        if (const char *e = getenv("PLS_HIP_RESIDENT_GRAM")) c->env.resident_gram = atoi(e);
-    }
+    pls_hip_context::read_env(c->env);
     c->device = device;
     c->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     if (hipSetDevice(device) != hipSuccess) { delete c; return PLS_HIP_ERR_DEVICE; }
@@ -293,8 +278,8 @@ int pls_hip_fit(pls_hip_handle h, const void *X, int64_t ldx, const void *Y, int
                 int64_t K, int64_t M, int64_t A, int method, int dtype, int mem, double *W, double *P,
                 double *Q, double *R, void *T, int64_t ldt, double *B) {
     CHK(check_handle(h));
-    if (dtype != PLS_HIP_F64 && dtype != PLS_HIP_F32) return fail(h, PLS_HIP_ERR_INVALID, "bad dtype");
-    if (mem != PLS_HIP_MEM_HOST && mem != PLS_HIP_MEM_DEVICE) return fail(h, PLS_HIP_ERR_INVALID, "bad mem kind");
+    CHK(check_dtype(h, dtype));
+    CHK(check_mem(h, mem));
     if (method != PLS_HIP_KERNEL_TYPE1 && method != PLS_HIP_KERNEL_TYPE2)
         return fail(h, PLS_HIP_ERR_INVALID, "bad method");
     const bool sharded = h->nranks > 1;
@@ -316,110 +301,37 @@ int pls_hip_fit(pls_hip_handle h, const void *X, int64_t ldx, const void *Y, int
     const size_t es = esize(dtype);
     const int Ki = (int)K, Mi = (int)M, Ai = (int)A;
 
+    // staging (host_entry.hpp); X last: once pre_xx / pre_xy point at its sums, nothing returns before they are cleared
     const void *dX = X, *dY = Y;
     void *dT = T;
     double *dW = W, *dP = P, *dQ = Q, *dR = R, *dB = B;
     i64 dldx = ldx, dldy = ldy, dldt = ldt;
-    if (mem == PLS_HIP_MEM_HOST) {
-        const i64 ldn = std::max<i64>(N, 1) + (std::max<i64>(N, 1) & 1);  // even ld keeps 16-B columns
-        CHK(ensure(h, h->hX, (size_t)ldn * K * es));
-        CHK(ensure(h, h->hY, (size_t)ldn * M * es));
-        CHK(ensure(h, h->hT, (size_t)ldn * A * es));
-        CHK(ensure(h, h->hW, (size_t)K * A * 8));
-        CHK(ensure(h, h->hP, (size_t)K * A * 8));
-        CHK(ensure(h, h->hR, (size_t)K * A * 8));
-        CHK(ensure(h, h->hQ, (size_t)M * A * 8));
-        CHK(ensure(h, h->hB, (size_t)K * M * 8));
-        CHK(h2d(h, h->hY.p, ldn, Y, ldy, N, M, es));
-        // A plan that works from X^T X (AUTO, GRAM, KERNEL_TYPE2) gets it for free: accumulated on the matrix cores
-        // row block by row block while X crosses PCIe (upload_accumulate).  Single rank only: the ranks of a sharded
-        // fit must not differ in their plan.
-        bool pre = false;
-        const bool wants_gram = h->opt_algo == PLS_HIP_ALGO_AUTO || h->opt_algo == PLS_HIP_ALGO_GRAM || method == PLS_HIP_KERNEL_TYPE2;
-        const bool single_launch = method == PLS_HIP_KERNEL_TYPE1 && h->opt_algo == PLS_HIP_ALGO_AUTO && h->opt_fuse &&
-                                   (plsk::tiny_fit_covers(N, Ki, Mi, Ai, ldn, es) || plsk::tiny_fit_m_covers(N, Ki, Mi, Ai, ldn, es) ||
-                                    plsk::micro_fit_covers(N, Ki, Mi, Ai, ldn, es));  // (no use for X^T X there)
-        if (wants_gram && !single_launch && !h->reducer && N > 0 && K <= 4096 && ensure(h, h->gxx, (size_t)K * K * 8) == PLS_HIP_OK &&
-            ensure(h, h->gxy, (size_t)K * M * 8) == PLS_HIP_OK) {
-            CHK(by_dtype(dtype, [&](auto t) {
-                using Tx = decltype(t);
-                return upload_accumulate<Tx>(h, (Tx *)h->hX.p, ldn, (const Tx *)X, ldx, N, Ki, (const Tx *)h->hY.p, ldn, Mi, (double *)h->gxx.p,
-                                            (double *)h->gxy.p, &pre);
-            }));
-        } else {
-            h->err.clear();
-            CHK(h2d(h, h->hX.p, ldn, X, ldx, N, K, es));
-        }
-        if (pre) {
-            h->pre_xx = (const double *)h->gxx.p;
-            h->pre_xy = (const double *)h->gxy.p;
-        }
-        dX = h->hX.p; dY = h->hY.p; dT = h->hT.p;
-        dW = (double *)h->hW.p; dP = (double *)h->hP.p; dQ = (double *)h->hQ.p; dR = (double *)h->hR.p;
-        dB = B ? (double *)h->hB.p : nullptr;
-        dldx = dldy = dldt = ldn;
-    }
-    // PLS_HIP_OPT_GRAPH: a repeated device-memory fit is replayed as one graph launch.  First occurrence of a call: eager (it
-    // also sizes every workspace); second: the same enqueue sequence under stream capture (nothing allocates any more),
-    // instantiated and launched; from the third on: hipGraphLaunch.  The kernel arguments are baked into the graph, so the key
-    // is everything they derive from.
-    // (a DUAL fit is never captured: it simply runs)
-    const bool graphable = h->opt_graph && mem == PLS_HIP_MEM_DEVICE && !h->reducer && h->opt_profile == 0 && !h->user_red &&
-                           h->stream != nullptr && !dual;  // (the legacy default stream cannot be captured)
-    std::vector<uint64_t> key;
-    if (graphable) {
-        key = {(uint64_t)(uintptr_t)X, (uint64_t)ldx, (uint64_t)(uintptr_t)Y, (uint64_t)ldy, (uint64_t)N, (uint64_t)K, (uint64_t)M,
-               (uint64_t)A, (uint64_t)method, (uint64_t)dtype, (uint64_t)(uintptr_t)W, (uint64_t)(uintptr_t)P, (uint64_t)(uintptr_t)Q,
-               (uint64_t)(uintptr_t)R, (uint64_t)(uintptr_t)T, (uint64_t)ldt, (uint64_t)(uintptr_t)B, (uint64_t)h->opt_algo,
-               (uint64_t)h->opt_fuse, (uint64_t)h->opt_power_iters, (uint64_t)h->opt_fused_grid, (uint64_t)h->opt_work_layout,
-               (uint64_t)h->opt_defer, (uint64_t)(uintptr_t)h->stream, (uint64_t)(uintptr_t)h->pre_xx, (uint64_t)(uintptr_t)h->pre_xy};
-        if (h->graph_exec && key == h->graph_key) {
-            HIPCHK(h, hipGraphLaunch(h->graph_exec, h->stream));
-            return PLS_HIP_OK;
-        }
-    }
-    const bool capture = graphable && key == h->graph_seen;
-    if (capture) {
-        if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; h->graph_key.clear(); }
-        HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    }
+    const i64 ldn = ld_even(N);
+    HostCall hc(h, mem);
+    CHK(hc.in(dY, dldy, Y, ldy, h->hY, N, M, es, ldn));
+    CHK(hc.out(dW, W, h->hW, K, A));
+    CHK(hc.out(dP, P, h->hP, K, A));
+    CHK(hc.out(dR, R, h->hR, K, A));
+    CHK(hc.out(dQ, Q, h->hQ, M, A));
+    CHK(hc.out(dB, B, h->hB, K, M));
+    CHK(hc.place(dT, dldt, h->hT, A, es, ldn));  // (KERNEL_TYPE2 has no scores: nothing to copy back)
+    if (method == PLS_HIP_KERNEL_TYPE1) CHK(hc.back(T, ldt, dT, dldt, N, A, es));
+    CHK(hc.place(dX, dldx, h->hX, K, es, ldn));
+    if (hc.host) CHK(upload_fit_x(h, const_cast<void *>(dX), dY, ldn, X, ldx, N, Ki, Mi, Ai, method, dtype));
+    // graph replay (fit_graph.hpp) around the A-loop
+    FitGraph g;
+    CHK(fit_graph_begin(h, g, X, ldx, Y, ldy, N, K, M, A, method, dtype, mem, W, P, Q, R, T, ldt, B, dual));
+    if (g.replayed) return PLS_HIP_OK;
     begin_fit_timing(h);
-    const int rc = by_dtype(dtype, [&](auto t) {
+    int rc = by_dtype(dtype, [&](auto t) {
         using Tx = decltype(t);
         return fit_device<Tx>(h, (const Tx *)dX, dldx, (const Tx *)dY, dldy, N, Ki, Mi, Ai, method, dW, dP, dQ, dR, (Tx *)dT, dldt, dB);
     });
     end_fit_timing(h);
-    if (capture) {
-        hipGraph_t graph = nullptr;
-        const hipError_t ce = hipStreamEndCapture(h->stream, &graph);
-        if (rc == PLS_HIP_OK && ce == hipSuccess && graph && hipGraphInstantiate(&h->graph_exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-            h->graph_key = key;
-            (void)hipGraphDestroy(graph);
-            HIPCHK(h, hipGraphLaunch(h->graph_exec, h->stream));  // this call's work
-        } else {
-            if (graph) (void)hipGraphDestroy(graph);
-            h->graph_exec = nullptr;
-            h->graph_seen.clear();
-            (void)hipGetLastError();
-            if (rc != PLS_HIP_OK) return rc;
-            return fail(h, PLS_HIP_ERR_DEVICE, "stream capture of the fit failed");
-        }
-    } else if (graphable) {
-        h->graph_seen = key;
-    }
-    if (mem == PLS_HIP_MEM_HOST) h->pre_xx = h->pre_xy = nullptr;
+    rc = fit_graph_end(h, g, rc);
+    if (hc.host) h->pre_xx = h->pre_xy = nullptr;
     if (rc != PLS_HIP_OK) return rc;
-    if (mem == PLS_HIP_MEM_HOST) {
-        CHK(d2h(h, W, K, dW, K, K, A, 8));
-        CHK(d2h(h, P, K, dP, K, K, A, 8));
-        CHK(d2h(h, R, K, dR, K, K, A, 8));
-        CHK(d2h(h, Q, M, dQ, M, M, A, 8));
-        if (B) CHK(d2h(h, B, K, dB, K, K, M, 8));
-        if (method == PLS_HIP_KERNEL_TYPE1) CHK(d2h(h, T, ldt, dT, dldt, N, A, es));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        CHK(check_diverged(h));
-    }
-    return PLS_HIP_OK;
+    return hc.finish(true);
 }
 
 int pls_hip_coefficients(pls_hip_handle h, const double *R, const double *Q, int64_t K, int64_t M,
@@ -428,71 +340,52 @@ int pls_hip_coefficients(pls_hip_handle h, const double *R, const double *Q, int
     if (!R || !Q || !B || K < 1 || M < 1 || A < 1 || cc < 0 || cc > A || K > (1 << 30))
         return fail(h, PLS_HIP_ERR_INVALID, "bad coefficients arguments");  // comp <= A: src/pls.cpp:445
     CHK(set_device(h));
+    CHK(check_mem(h, mem));
     const double *dR = R, *dQ = Q;
     double *dB = B;
-    if (mem == PLS_HIP_MEM_HOST) {
-        CHK(ensure(h, h->hR, (size_t)K * A * 8));
-        CHK(ensure(h, h->hQ, (size_t)M * A * 8));
-        CHK(ensure(h, h->hB, (size_t)K * M * 8));
-        CHK(h2d(h, h->hR.p, K, R, K, K, A, 8));
-        CHK(h2d(h, h->hQ.p, M, Q, M, M, A, 8));
-        dR = (double *)h->hR.p; dQ = (double *)h->hQ.p; dB = (double *)h->hB.p;
-    } else if (mem != PLS_HIP_MEM_DEVICE) {
-        return fail(h, PLS_HIP_ERR_INVALID, "bad mem kind");
-    }
+    HostCall hc(h, mem);
+    CHK(hc.in(dR, R, h->hR, K, A));
+    CHK(hc.in(dQ, Q, h->hQ, M, A));
+    CHK(hc.out(dB, B, h->hB, K, M));
     const int nblk = (int)((K * M + plsk::WG - 1) / plsk::WG);
     hipLaunchKernelGGL(plsk::coefficients_kernel, dim3(nblk), dim3(plsk::WG), 0, h->stream, dR, dQ,
                        (int)K, (int)M, (int)cc, dB);
     LAUNCH_CHECK(h);
-    if (mem == PLS_HIP_MEM_HOST) {
-        CHK(d2h(h, B, K, dB, K, K, M, 8));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return PLS_HIP_OK;
+    return hc.finish();
 }
 
 int pls_hip_xb(pls_hip_handle h, const void *X, int64_t ldx, int64_t N, int64_t K, const double *Bm,
                int64_t ldb, int64_t C, int dtype, int mem, void *out, int64_t ldo) {
     CHK(check_handle(h));
-    if (dtype != PLS_HIP_F64 && dtype != PLS_HIP_F32) return fail(h, PLS_HIP_ERR_INVALID, "bad dtype");
+    CHK(check_dtype(h, dtype));
     if (N < 0 || K < 1 || C < 1 || K > (1 << 30) || C > (1 << 20) || ldb < K ||
         ldx < std::max<i64>(N, 1) || ldo < std::max<i64>(N, 1) || !Bm || (N > 0 && (!X || !out)))
         return fail(h, PLS_HIP_ERR_INVALID, "bad xb arguments");
     if (N == 0) return PLS_HIP_OK;
     CHK(set_device(h));
+    CHK(check_mem(h, mem));
     const size_t es = esize(dtype);
     const void *dX = X;
     const double *dBm = Bm;
     void *dO = out;
     i64 dldx = ldx, dldo = ldo, dldb = ldb;
-    if (mem == PLS_HIP_MEM_HOST) {
-        const i64 ldn = N + (N & 1);
-        CHK(ensure(h, h->hIn, (size_t)ldn * K * es));
-        CHK(ensure(h, h->hOut, (size_t)ldn * C * es));
-        CHK(ensure(h, h->hB, (size_t)K * C * 8));
-        CHK(h2d(h, h->hIn.p, ldn, X, ldx, N, K, es));
-        CHK(h2d(h, h->hB.p, K, Bm, ldb, K, C, 8));
-        dX = h->hIn.p; dO = h->hOut.p; dBm = (const double *)h->hB.p;
-        dldx = dldo = ldn; dldb = K;
-    } else if (mem != PLS_HIP_MEM_DEVICE) {
-        return fail(h, PLS_HIP_ERR_INVALID, "bad mem kind");
-    }
+    const i64 ldn = ld_even(N);
+    HostCall hc(h, mem);
+    CHK(hc.in(dX, dldx, X, ldx, h->hIn, N, K, es, ldn));
+    CHK(hc.in(dBm, dldb, Bm, ldb, h->hB, K, C, 8, K));
+    CHK(hc.out(dO, dldo, out, ldo, h->hOut, N, C, es, ldn));
     int nss = 0;
     CHK(by_dtype(dtype, [&](auto t) {
         using T = decltype(t);
         return launch_xb<T>(h, (const T *)dX, dldx, N, (int)K, dBm, dldb, (int)C, (T *)dO, dldo, nullptr, &nss);
     }));
-    if (mem == PLS_HIP_MEM_HOST) {
-        CHK(d2h(h, out, ldo, dO, dldo, N, C, es));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return PLS_HIP_OK;
+    return hc.finish();
 }
 
 int pls_hip_xty(pls_hip_handle h, const void *X, int64_t ldx, const void *Y, int64_t ldy, int64_t N,
                 int64_t K, int64_t M, int dtype, double *XY) {
     CHK(check_handle(h));
-    if (dtype != PLS_HIP_F64 && dtype != PLS_HIP_F32) return fail(h, PLS_HIP_ERR_INVALID, "bad dtype");
+    CHK(check_dtype(h, dtype));
     if (N < 1 || K < 1 || M < 1 || K > (1 << 30) || M > (1 << 20) || !X || !Y || !XY || ldx < N || ldy < N)
         return fail(h, PLS_HIP_ERR_INVALID, "bad xty arguments");
     CHK(set_device(h));
@@ -514,7 +407,7 @@ int pls_hip_xty(pls_hip_handle h, const void *X, int64_t ldx, const void *Y, int
 int pls_hip_deflate(pls_hip_handle h, const void *src, int64_t lds, void *dst, int64_t ldd, int64_t N,
                     int64_t K, const void *t, const double *p, int dtype) {
     CHK(check_handle(h));
-    if (dtype != PLS_HIP_F64 && dtype != PLS_HIP_F32) return fail(h, PLS_HIP_ERR_INVALID, "bad dtype");
+    CHK(check_dtype(h, dtype));
     if (N < 1 || K < 1 || K > (1 << 30) || !src || !dst || !t || !p || lds < N || ldd < N)
         return fail(h, PLS_HIP_ERR_INVALID, "bad deflate arguments");
     CHK(set_device(h));
@@ -524,17 +417,10 @@ int pls_hip_deflate(pls_hip_handle h, const void *src, int64_t lds, void *dst, i
     });
 }
 
-}  // extern "C"
-
-#include "plan_stats.hpp"
-
-
-extern "C" {
-
 int pls_hip_colwise_z_scores(pls_hip_handle h, const void *X, int64_t ldx, int64_t N, int64_t n_total,
                              int64_t K, int dtype, void *Z, int64_t ldz, double *mean, double *sd) {
     CHK(check_handle(h));
-    if (dtype != PLS_HIP_F64 && dtype != PLS_HIP_F32) return fail(h, PLS_HIP_ERR_INVALID, "bad dtype");
+    CHK(check_dtype(h, dtype));
     if (N < 0 || n_total < N || n_total < 1 || K < 1 || K > (1 << 30) || !mean || !sd || (N > 0 && !X) ||
         ldx < std::max<i64>(N, 1) || (Z && ldz < std::max<i64>(N, 1)))
         return fail(h, PLS_HIP_ERR_INVALID, "bad z-score arguments");
@@ -548,7 +434,7 @@ int pls_hip_colwise_z_scores(pls_hip_handle h, const void *X, int64_t ldx, int64
 int pls_hip_sse_by_components(pls_hip_handle h, const void *S, int64_t lds, const void *Y, int64_t ldy,
                               int64_t N, int64_t A, int64_t M, const double *Q, int dtype, double *SSE) {
     CHK(check_handle(h));
-    if (dtype != PLS_HIP_F64 && dtype != PLS_HIP_F32) return fail(h, PLS_HIP_ERR_INVALID, "bad dtype");
+    CHK(check_dtype(h, dtype));
     if (N < 1 || A < 1 || M < 1 || M > 1024 || A > (1 << 20) || !S || !Y || !Q || !SSE || lds < N || ldy < N)
         return fail(h, PLS_HIP_ERR_INVALID, "bad sse arguments");
     CHK(set_device(h));
@@ -558,27 +444,12 @@ int pls_hip_sse_by_components(pls_hip_handle h, const void *S, int64_t lds, cons
     });
 }
 
-}  // extern "C"
-
-#include "plan_cv.hpp"
-#include "dual_round.hpp"
-#include "plan_dual_cv.hpp"
-#include "plan_dual_batch.hpp"
-#include "plan_batch.hpp"
-#include "plan_resample.hpp"
-#include "plan_dual_cvbatch.hpp"
-#include "plan_missing.hpp"
-#include "plan_missing_cv.hpp"
-
-
-extern "C" {
-
 int pls_hip_cv_folds(pls_hip_handle h, const void *X, int64_t ldx, const void *Y, int64_t ldy, int64_t N,
                      int64_t K, int64_t M, int64_t A, const int64_t *test_idx, int64_t test_size,
                      int64_t num_folds, int dtype, int mem, double *E) {
     CHK(check_handle(h));
-    if (dtype != PLS_HIP_F64 && dtype != PLS_HIP_F32) return fail(h, PLS_HIP_ERR_INVALID, "bad dtype");
-    if (mem != PLS_HIP_MEM_HOST && mem != PLS_HIP_MEM_DEVICE) return fail(h, PLS_HIP_ERR_INVALID, "bad mem kind");
+    CHK(check_dtype(h, dtype));
+    CHK(check_mem(h, mem));
     if (h->reducer) {  // a collective: local checks here, the ones on global data after the partition message
         if (N < 0 || K < 1 || M < 1 || A < 1 || A > K || K > (1 << 30) || (N > 0 && (!X || !Y)) || !test_idx || !E ||
             test_size < 1 || num_folds < 1 || ldx < std::max<i64>(N, 1) || ldy < std::max<i64>(N, 1) ||
@@ -594,23 +465,18 @@ int pls_hip_cv_folds(pls_hip_handle h, const void *X, int64_t ldx, const void *Y
         return fail(h, PLS_HIP_ERR_INVALID, "bad cv_folds arguments");
     if (M > plsk::LM_MAX) return fail(h, PLS_HIP_ERR_UNSUPPORTED, "more than 1024 responses not supported on the device");
     const i64 nobs = num_folds * test_size;
-    for (i64 j = 0; j < nobs; ++j)
-        if (test_idx[j] < 0 || test_idx[j] >= N) return fail(h, PLS_HIP_ERR_INVALID, "cv_folds: test index out of range");
+    CHK(check_test_idx(h, test_idx, nobs, N, "cv_folds"));
     CHK(set_device(h));
     const size_t es = esize(dtype);
     const void *dX = X, *dY = Y;
+    double *dE = E;
     i64 dldx = ldx, dldy = ldy;
-    if (mem == PLS_HIP_MEM_HOST) {
-        const i64 ldn = N + ((-N) & 3);  // 16-byte columns for either type
-        CHK(ensure(h, h->hX, (size_t)ldn * K * es));
-        CHK(ensure(h, h->hY, (size_t)ldn * M * es));
-        CHK(h2d(h, h->hX.p, ldn, X, ldx, N, K, es));
-        CHK(h2d(h, h->hY.p, ldn, Y, ldy, N, M, es));
-        dX = h->hX.p; dY = h->hY.p;
-        dldx = dldy = ldn;
-    }
-    CHK(ensure(h, h->cve, (size_t)nobs * A * M * 8));
-    double *dE = (mem == PLS_HIP_MEM_HOST) ? (double *)h->cve.p : E;
+    const i64 ldn = ld_quad(N);
+    HostCall hc(h, mem);
+    CHK(hc.in(dX, dldx, X, ldx, h->hX, N, K, es, ldn));
+    CHK(hc.in(dY, dldy, Y, ldy, h->hY, N, M, es, ldn));
+    CHK(ensure(h, h->cve, (size_t)nobs * A * M * 8));  // (for device memory too, as ever)
+    CHK(hc.out_flat(dE, E, h->cve, (size_t)nobs * A * M * 8));
     int rc = PLS_HIP_ERR_ALLOC;
     const bool tiny = M == 1 && plsk::tiny_fit_covers(N, (int)K, 1, (int)A, dldx, es) && !h->env.cv_refit && h->env.tiny;
     const bool tiny_m = plsk::tiny_fit_m_covers(N, (int)K, (int)M, (int)A, dldx, es) && !h->env.cv_refit && h->env.tiny;
@@ -648,18 +514,15 @@ int pls_hip_cv_folds(pls_hip_handle h, const void *X, int64_t ldx, const void *Y
         });
     }
     if (rc != PLS_HIP_OK) return rc;
-    if (mem == PLS_HIP_MEM_HOST)
-        HIPCHK(h, hipMemcpyAsync(E, dE, (size_t)nobs * A * M * 8, hipMemcpyDeviceToHost, h->stream));
-    // the index list is host memory of the caller: the copy above must have consumed it before we return
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return PLS_HIP_OK;
+    // the index list is host memory of the caller: the work must have consumed it before we return, whatever `mem` is
+    return hc.finish(false, true);
 }
 
 int pls_hip_fit_batch(pls_hip_handle h, const void *X, int64_t ldx, const void *Ys, int64_t ldy, int64_t N, int64_t K, int64_t M,
                       int64_t A, int64_t nprob, int dtype, int mem, double *R, double *Q, double *tt, double *B, double *ssy) {
     CHK(check_handle(h));
-    if (dtype != PLS_HIP_F64 && dtype != PLS_HIP_F32) return fail(h, PLS_HIP_ERR_INVALID, "bad dtype");
-    if (mem != PLS_HIP_MEM_HOST && mem != PLS_HIP_MEM_DEVICE) return fail(h, PLS_HIP_ERR_INVALID, "bad mem kind");
+    CHK(check_dtype(h, dtype));
+    CHK(check_mem(h, mem));
     const bool empty_member = (N == 0 && h->nranks > 1);  // an empty shard still takes part in the messages
     const i64 n1 = std::max<i64>(N, 1);
     if (N < 0 || (N == 0 && !empty_member) || K < 1 || M < 1 || A < 1 || A > K || nprob < 1 || K > (1 << 30) || M > (1 << 20) ||
@@ -673,13 +536,12 @@ int pls_hip_fit_resampled(pls_hip_handle h, const void *X, int64_t ldx, const vo
                           int64_t A, const double *Wt, int64_t ldw, int64_t nrep, int dtype, int mem, double *Q, double *tt, double *B,
                           double *B0, double *Bmean, double *Bm2) {
     CHK(check_handle(h));
-    if (dtype != PLS_HIP_F64 && dtype != PLS_HIP_F32) return fail(h, PLS_HIP_ERR_INVALID, "bad dtype");
-    if (mem != PLS_HIP_MEM_HOST && mem != PLS_HIP_MEM_DEVICE) return fail(h, PLS_HIP_ERR_INVALID, "bad mem kind");
+    CHK(check_dtype(h, dtype));
+    CHK(check_mem(h, mem));
     if (N < 1 || K < 1 || M < 1 || A < 1 || A > K || nrep < 1 || K > (1 << 30) || M > (1 << 20) || nrep > (1 << 24) ||
         nrep * M > (1 << 30) || !X || !Y || !Wt || ldx < N || ldy < N || ldw < N)
         return fail(h, PLS_HIP_ERR_INVALID, "bad fit_resampled arguments: need N>=1, 1<=A<=K, M>=1, nrep>=1, ld>=N, X, Y and Wt");
-    if (h->reducer || h->nranks > 1)
-        return fail(h, PLS_HIP_ERR_UNSUPPORTED, "fit_resampled needs every row of X on one handle: not on a row-sharded handle");
+    CHK(check_unsharded(h, "fit_resampled needs every row of X on one handle: not on a row-sharded handle"));
     // what the general route's pls_hip_fit would refuse, before anything is written
     if (!resample_dual_covers(h, N, M)) {
         if (M > plsk::LM_MAX) return fail(h, PLS_HIP_ERR_UNSUPPORTED, "more than 1024 responses not supported on the device");
@@ -694,17 +556,14 @@ int pls_hip_cv_press_batch(pls_hip_handle h, const void *X, int64_t ldx, const v
                            int64_t A, int64_t nprob, const int64_t *test_idx, int64_t test_size, int64_t num_folds, int dtype, int mem,
                            double *PRESS, double *ssy, double *E) {
     CHK(check_handle(h));
-    if (dtype != PLS_HIP_F64 && dtype != PLS_HIP_F32) return fail(h, PLS_HIP_ERR_INVALID, "bad dtype");
-    if (mem != PLS_HIP_MEM_HOST && mem != PLS_HIP_MEM_DEVICE) return fail(h, PLS_HIP_ERR_INVALID, "bad mem kind");
+    CHK(check_dtype(h, dtype));
+    CHK(check_mem(h, mem));
     if (N < 2 || K < 1 || M < 1 || A < 1 || A > K || K > (1 << 30) || nprob < 1 || nprob > (1 << 24) || nprob * M > (1 << 30) || !X ||
         !Ys || !test_idx || test_size < 1 || test_size >= N || num_folds < 1 || ldx < N || ldy < N || num_folds > (1 << 22) ||
         test_size > (1 << 20))
         return fail(h, PLS_HIP_ERR_INVALID, "bad cv_press_batch arguments: need N>=2, 1<=A<=K, M>=1, nprob>=1, 1<=test_size<N, ld>=N, X, Ys and test_idx");
-    const i64 nobs = num_folds * test_size;
-    for (i64 j = 0; j < nobs; ++j)
-        if (test_idx[j] < 0 || test_idx[j] >= N) return fail(h, PLS_HIP_ERR_INVALID, "cv_press_batch: test index out of range");
-    if (h->reducer || h->nranks > 1)
-        return fail(h, PLS_HIP_ERR_UNSUPPORTED, "cv_press_batch needs every row of X on one handle: not on a row-sharded handle");
+    CHK(check_test_idx(h, test_idx, num_folds * test_size, N, "cv_press_batch"));
+    CHK(check_unsharded(h, "cv_press_batch needs every row of X on one handle: not on a row-sharded handle"));
     if (M > plsk::LM_MAX) return fail(h, PLS_HIP_ERR_UNSUPPORTED, "more than 1024 responses not supported on the device");
     CHK(set_device(h));
     return cv_press_batch_impl(h, X, ldx, Ys, ldy, N, K, M, A, nprob, test_idx, test_size, num_folds, dtype, mem, PRESS, ssy, E);
@@ -714,33 +573,25 @@ int pls_hip_model_sse(pls_hip_handle h, const void *X, int64_t ldx, const void *
                       int64_t K, int64_t M, int64_t A, const double *R, const double *Q, int dtype, int mem,
                       double *SSE) {
     CHK(check_handle(h));
-    if (dtype != PLS_HIP_F64 && dtype != PLS_HIP_F32) return fail(h, PLS_HIP_ERR_INVALID, "bad dtype");
-    if (mem != PLS_HIP_MEM_HOST && mem != PLS_HIP_MEM_DEVICE) return fail(h, PLS_HIP_ERR_INVALID, "bad mem kind");
+    CHK(check_dtype(h, dtype));
+    CHK(check_mem(h, mem));
     const bool empty_member = (N == 0 && h->nranks > 1);  // an empty shard still takes part in the reduction
     if (N < 0 || (N == 0 && !empty_member) || K < 1 || M < 1 || A < 1 || M > 1024 || A > (1 << 20) || K > (1 << 30) ||
         (N > 0 && (!X || !Y)) || !R || !Q || !SSE || ldx < std::max<i64>(N, 1) || ldy < std::max<i64>(N, 1))
         return fail(h, PLS_HIP_ERR_INVALID, "bad model_sse arguments");
     CHK(set_device(h));
     const size_t es = esize(dtype);
-    const i64 ldn = std::max<i64>(N, 1) + (std::max<i64>(N, 1) & 1);
+    const i64 ldn = ld_even(N);  // (of the scores for device memory too)
     const void *dX = X, *dY = Y;
     const double *dR = R, *dQ = Q;
     double *dE = SSE;
     i64 dldx = ldx, dldy = ldy;
-    if (mem == PLS_HIP_MEM_HOST) {
-        CHK(ensure(h, h->hIn, (size_t)ldn * K * es));
-        CHK(ensure(h, h->hY, (size_t)ldn * M * es));
-        CHK(ensure(h, h->hR, (size_t)K * A * 8));
-        CHK(ensure(h, h->hQ, (size_t)M * A * 8));
-        CHK(ensure(h, h->hB, (size_t)M * A * 8));
-        CHK(h2d(h, h->hIn.p, ldn, X, ldx, N, K, es));
-        CHK(h2d(h, h->hY.p, ldn, Y, ldy, N, M, es));
-        CHK(h2d(h, h->hR.p, K, R, K, K, A, 8));
-        CHK(h2d(h, h->hQ.p, M, Q, M, M, A, 8));
-        dX = h->hIn.p; dY = h->hY.p; dR = (const double *)h->hR.p; dQ = (const double *)h->hQ.p;
-        dE = (double *)h->hB.p;
-        dldx = dldy = ldn;
-    }
+    HostCall hc(h, mem);
+    CHK(hc.in(dX, dldx, X, ldx, h->hIn, N, K, es, ldn));
+    CHK(hc.in(dY, dldy, Y, ldy, h->hY, N, M, es, ldn));
+    CHK(hc.in(dR, R, h->hR, K, A));
+    CHK(hc.in(dQ, Q, h->hQ, M, A));
+    CHK(hc.out(dE, SSE, h->hB, M, A));
     CHK(ensure(h, h->hOut, (size_t)ldn * A * es));  // the scores S = X R stay on the device
     int nss = 0;
     CHK(by_dtype(dtype, [&](auto t) -> int {
@@ -748,17 +599,13 @@ int pls_hip_model_sse(pls_hip_handle h, const void *X, int64_t ldx, const void *
         if (N > 0) CHK(launch_xb<T>(h, (const T *)dX, dldx, N, (int)K, dR, K, (int)A, (T *)h->hOut.p, ldn, nullptr, &nss));
         return sse_device<T>(h, (const T *)h->hOut.p, ldn, (const T *)dY, dldy, N, (int)A, (int)M, dQ, dE);
     }));
-    if (mem == PLS_HIP_MEM_HOST) {
-        CHK(d2h(h, SSE, M, dE, M, M, A, 8));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return PLS_HIP_OK;
+    return hc.finish();
 }
 
 int pls_hip_validation(pls_hip_handle h, const double *E, int64_t nobs, int64_t A, int64_t M, int mem, double *PRESS, double *D,
                        double *probw, int64_t *ref) {
     CHK(check_handle(h));
-    if (mem != PLS_HIP_MEM_HOST && mem != PLS_HIP_MEM_DEVICE) return fail(h, PLS_HIP_ERR_INVALID, "bad mem kind");
+    CHK(check_mem(h, mem));
     if (!E || nobs < 1 || A < 1 || M < 1) return fail(h, PLS_HIP_ERR_INVALID, "bad validation arguments");
     if (nobs > ((i64)1 << 31) - 1 || A > (1 << 20) || M > (1 << 20) || M * A > (1 << 24) ||
         ((nobs + plsk::VAL_CH - 1) / plsk::VAL_CH) * M * A > ((i64)1 << 31) - 1)
@@ -772,8 +619,8 @@ int pls_hip_x_diagnostics(pls_hip_handle h, const void *X, int64_t ldx, int64_t 
                           const double *R, const double *P, const double *tvar, int dtype, int mem, double *Qres, int64_t ldq,
                           double *T2, int64_t ldt2, void *S, int64_t lds, double *ssx, double *sst) {
     CHK(check_handle(h));
-    if (dtype != PLS_HIP_F64 && dtype != PLS_HIP_F32) return fail(h, PLS_HIP_ERR_INVALID, "bad dtype");
-    if (mem != PLS_HIP_MEM_HOST && mem != PLS_HIP_MEM_DEVICE) return fail(h, PLS_HIP_ERR_INVALID, "bad mem kind");
+    CHK(check_dtype(h, dtype));
+    CHK(check_mem(h, mem));
     const bool empty_member = (N == 0 && h->nranks > 1);  // an empty shard still takes part in the message
     const i64 n1 = std::max<i64>(N, 1);
     if (N < 0 || (N == 0 && !empty_member) || n_total < N || n_total < 1 || K < 1 || A < 1 || A > K || A > (1 << 20) ||
@@ -787,57 +634,38 @@ int pls_hip_x_diagnostics(pls_hip_handle h, const void *X, int64_t ldx, int64_t 
     double *dQ = Qres, *dT2 = T2, *dssx = ssx, *dsst = sst;
     void *dS = S;
     i64 dldx = ldx, dldq = ldq, dldt2 = ldt2, dlds = lds;
-    if (mem == PLS_HIP_MEM_HOST) {
-        const i64 ldn = n1 + (n1 & 1);
-        CHK(ensure(h, h->hIn, (size_t)ldn * K * es));
-        CHK(ensure(h, h->hR, (size_t)K * A * 8));
-        CHK(ensure(h, h->hP, (size_t)K * A * 8));
-        CHK(ensure(h, h->xdsmall, (size_t)(3 * A + 1) * 8));  // [tvar (A), ssx (A + 1), sst (A)]
-        if (Qres) CHK(ensure(h, h->xdoQ, (size_t)ldn * A * 8));
-        if (T2) CHK(ensure(h, h->xdoT, (size_t)ldn * A * 8));
-        if (S) CHK(ensure(h, h->xdoS, (size_t)ldn * A * es));
-        CHK(h2d(h, h->hIn.p, ldn, X, ldx, N, K, es));
-        CHK(h2d(h, h->hR.p, K, R, K, K, A, 8));
-        CHK(h2d(h, h->hP.p, K, P, K, K, A, 8));
-        double *small = (double *)h->xdsmall.p;
-        if (tvar) CHK(h2d(h, small, A, tvar, A, A, 1, 8));
-        dX = h->hIn.p; dR = (const double *)h->hR.p; dP = (const double *)h->hP.p;
-        dtv = tvar ? small : nullptr;
-        dQ = Qres ? (double *)h->xdoQ.p : nullptr;
-        dT2 = T2 ? (double *)h->xdoT.p : nullptr;
-        dS = S ? h->xdoS.p : nullptr;
-        dssx = ssx ? small + A : nullptr;
-        dsst = sst ? small + 2 * A + 1 : nullptr;
-        dldx = dldq = dldt2 = dlds = ldn;
-    }
+    const i64 ldn = ld_even(N);
+    const size_t small = (size_t)(3 * A + 1) * 8;  // xdsmall = [tvar (A), ssx (A + 1), sst (A)]
+    HostCall hc(h, mem);
+    CHK(hc.in(dX, dldx, X, ldx, h->hIn, N, K, es, ldn));
+    CHK(hc.in(dR, R, h->hR, K, A));
+    CHK(hc.in(dP, P, h->hP, K, A));
+    if (tvar) CHK(hc.in(dtv, tvar, h->xdsmall, A, 1, 8, small, 0));
+    CHK(hc.out(dQ, dldq, Qres, ldq, h->xdoQ, N, A, 8, ldn));
+    CHK(hc.out(dT2, dldt2, T2, ldt2, h->xdoT, N, A, 8, ldn));
+    CHK(hc.out(dS, dlds, S, lds, h->xdoS, N, A, es, ldn));
+    CHK(hc.out(dssx, ssx, h->xdsmall, A + 1, 1, 8, small, (size_t)A * 8));
+    CHK(hc.out(dsst, sst, h->xdsmall, A, 1, 8, small, (size_t)(2 * A + 1) * 8));
+    if (hc.host) dldq = dldt2 = dlds = ldn;  // (of an output that is not asked for as well)
     CHK(by_dtype(dtype, [&](auto t) {
         using T = decltype(t);
         return xdiag_device<T>(h, (const T *)dX, dldx, N, n_total, (int)K, (int)A, dR, dP, dtv, dQ, dldq, dT2, dldt2, (T *)dS, dlds, dssx,
                                dsst);
     }));
-    if (mem == PLS_HIP_MEM_HOST) {
-        if (Qres) CHK(d2h(h, Qres, ldq, dQ, dldq, N, A, 8));
-        if (T2) CHK(d2h(h, T2, ldt2, dT2, dldt2, N, A, 8));
-        if (S) CHK(d2h(h, S, lds, dS, dlds, N, A, es));
-        if (ssx) CHK(d2h(h, ssx, A + 1, dssx, A + 1, A + 1, 1, 8));
-        if (sst) CHK(d2h(h, sst, A, dsst, A, A, 1, 8));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return PLS_HIP_OK;
+    return hc.finish();
 }
 
 int pls_hip_fit_missing(pls_hip_handle h, const void *X, int64_t ldx, const void *Y, int64_t ldy, int64_t N, int64_t K, int64_t M,
                         int64_t A, int dtype, int mem, double *W, double *P, double *Q, double *R, void *T, int64_t ldt, double *B,
                         int64_t *iters) {
     CHK(check_handle(h));
-    if (dtype != PLS_HIP_F64 && dtype != PLS_HIP_F32) return fail(h, PLS_HIP_ERR_INVALID, "bad dtype");
-    if (mem != PLS_HIP_MEM_HOST && mem != PLS_HIP_MEM_DEVICE) return fail(h, PLS_HIP_ERR_INVALID, "bad mem kind");
+    CHK(check_dtype(h, dtype));
+    CHK(check_mem(h, mem));
     if (N < 1 || K < 1 || M < 1 || A < 1 || A > K || !X || !Y || !W || !P || !Q || !R || !T || ldx < N || ldy < N || ldt < N)
         return fail(h, PLS_HIP_ERR_INVALID, "bad fit_missing arguments: need N>=1, 1<=A<=K, M>=1, ld>=N, X, Y, W, P, Q, R and T");
     if (K > (((i64)1 << 31) - 1) || M > plsk::MISS_MAX_M)
         return fail(h, PLS_HIP_ERR_UNSUPPORTED, "fit_missing takes at most 32 responses (and K < 2^31)");
-    if (h->reducer || h->nranks > 1)
-        return fail(h, PLS_HIP_ERR_UNSUPPORTED, "fit_missing needs every row of X on one handle: not on a row-sharded handle");
+    CHK(check_unsharded(h, "fit_missing needs every row of X on one handle: not on a row-sharded handle"));
     CHK(set_device(h));
     const size_t es = esize(dtype);
     const void *dX = X, *dY = Y;
@@ -845,25 +673,17 @@ int pls_hip_fit_missing(pls_hip_handle h, const void *X, int64_t ldx, const void
     double *dW = W, *dP = P, *dQ = Q, *dR = R, *dB = B;
     long long *dit = (long long *)iters;
     i64 dldx = ldx, dldy = ldy, dldt = ldt;
-    if (mem == PLS_HIP_MEM_HOST) {
-        const i64 ldn = N + ((-N) & 3);  // 16-byte columns for either type
-        CHK(ensure(h, h->hX, (size_t)ldn * K * es));
-        CHK(ensure(h, h->hY, (size_t)ldn * M * es));
-        CHK(ensure(h, h->hT, (size_t)ldn * A * es));
-        CHK(ensure(h, h->hW, (size_t)K * A * 8));
-        CHK(ensure(h, h->hP, (size_t)K * A * 8));
-        CHK(ensure(h, h->hR, (size_t)K * A * 8));
-        CHK(ensure(h, h->hQ, (size_t)M * A * 8));
-        if (B) CHK(ensure(h, h->hB, (size_t)K * M * 8));
-        if (iters) CHK(ensure(h, h->mit, (size_t)A * 8));
-        CHK(h2d(h, h->hX.p, ldn, X, ldx, N, K, es));
-        CHK(h2d(h, h->hY.p, ldn, Y, ldy, N, M, es));
-        dX = h->hX.p; dY = h->hY.p; dT = h->hT.p;
-        dW = (double *)h->hW.p; dP = (double *)h->hP.p; dQ = (double *)h->hQ.p; dR = (double *)h->hR.p;
-        dB = B ? (double *)h->hB.p : nullptr;
-        dit = iters ? (long long *)h->mit.p : nullptr;
-        dldx = dldy = dldt = ldn;
-    }
+    const i64 ldn = ld_quad(N);
+    HostCall hc(h, mem);
+    CHK(hc.in(dX, dldx, X, ldx, h->hX, N, K, es, ldn));
+    CHK(hc.in(dY, dldy, Y, ldy, h->hY, N, M, es, ldn));
+    CHK(hc.out(dW, W, h->hW, K, A));
+    CHK(hc.out(dP, P, h->hP, K, A));
+    CHK(hc.out(dR, R, h->hR, K, A));
+    CHK(hc.out(dQ, Q, h->hQ, M, A));
+    CHK(hc.out(dB, B, h->hB, K, M));
+    CHK(hc.out(dT, dldt, T, ldt, h->hT, N, A, es, ldn));
+    CHK(hc.out(dit, iters, h->mit, A, 1));
     begin_fit_timing(h);
     const int rc = by_dtype(dtype, [&](auto t) {
         using Tx = decltype(t);
@@ -872,32 +692,21 @@ int pls_hip_fit_missing(pls_hip_handle h, const void *X, int64_t ldx, const void
     });
     end_fit_timing(h);
     if (rc != PLS_HIP_OK) return rc;
-    if (mem == PLS_HIP_MEM_HOST) {
-        CHK(d2h(h, W, K, dW, K, K, A, 8));
-        CHK(d2h(h, P, K, dP, K, K, A, 8));
-        CHK(d2h(h, R, K, dR, K, K, A, 8));
-        CHK(d2h(h, Q, M, dQ, M, M, A, 8));
-        if (B) CHK(d2h(h, B, K, dB, K, K, M, 8));
-        CHK(d2h(h, T, ldt, dT, dldt, N, A, es));
-        if (iters) CHK(d2h(h, iters, A, dit, A, A, 1, 8));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return PLS_HIP_OK;
+    return hc.finish();
 }
 
 int pls_hip_cv_folds_missing(pls_hip_handle h, const void *X, int64_t ldx, const void *Y, int64_t ldy, int64_t N, int64_t K, int64_t M,
                              int64_t A, const int64_t *test_idx, int64_t test_size, int64_t num_folds, int dtype, int mem, double *E,
                              int64_t *iters) {
     CHK(check_handle(h));
-    if (dtype != PLS_HIP_F64 && dtype != PLS_HIP_F32) return fail(h, PLS_HIP_ERR_INVALID, "bad dtype");
-    if (mem != PLS_HIP_MEM_HOST && mem != PLS_HIP_MEM_DEVICE) return fail(h, PLS_HIP_ERR_INVALID, "bad mem kind");
+    CHK(check_dtype(h, dtype));
+    CHK(check_mem(h, mem));
     if (N < 2 || K < 1 || M < 1 || A < 1 || A > K || !X || !Y || !test_idx || !E || test_size < 1 || test_size >= N || num_folds < 1 ||
         ldx < N || ldy < N || num_folds > (1 << 22) || test_size > (1 << 20))
         return fail(h, PLS_HIP_ERR_INVALID, "bad cv_folds_missing arguments: need N>=2, 1<=A<=K, M>=1, ld>=N, 1<=test_size<N, X, Y, test_idx and E");
     if (K > (((i64)1 << 31) - 1) || M > plsk::MISS_MAX_M)
         return fail(h, PLS_HIP_ERR_UNSUPPORTED, "cv_folds_missing takes at most 32 responses (and K < 2^31)");
-    if (h->reducer || h->nranks > 1)
-        return fail(h, PLS_HIP_ERR_UNSUPPORTED, "cv_folds_missing needs every row of X on one handle: not on a row-sharded handle");
+    CHK(check_unsharded(h, "cv_folds_missing needs every row of X on one handle: not on a row-sharded handle"));
     const i64 nobs = num_folds * test_size;
     {
         std::unique_ptr<i64[]> fold_of(new (std::nothrow) i64[(size_t)N]);  // the last fold that held a row out
@@ -916,18 +725,12 @@ int pls_hip_cv_folds_missing(pls_hip_handle h, const void *X, int64_t ldx, const
     double *dE = E;
     long long *dit = (long long *)iters;
     i64 dldx = ldx, dldy = ldy;
-    if (mem == PLS_HIP_MEM_HOST) {
-        const i64 ldn = N + ((-N) & 3);  // 16-byte columns for either type
-        CHK(ensure(h, h->hX, (size_t)ldn * K * es));
-        CHK(ensure(h, h->hY, (size_t)ldn * M * es));
-        CHK(ensure(h, h->cve, (size_t)nobs * A * M * 8));
-        if (iters) CHK(ensure(h, h->mit, (size_t)num_folds * A * 8));
-        CHK(h2d(h, h->hX.p, ldn, X, ldx, N, K, es));
-        CHK(h2d(h, h->hY.p, ldn, Y, ldy, N, M, es));
-        dX = h->hX.p; dY = h->hY.p; dE = (double *)h->cve.p;
-        dit = iters ? (long long *)h->mit.p : nullptr;
-        dldx = dldy = ldn;
-    }
+    const i64 ldn = ld_quad(N);
+    HostCall hc(h, mem);
+    CHK(hc.in(dX, dldx, X, ldx, h->hX, N, K, es, ldn));
+    CHK(hc.in(dY, dldy, Y, ldy, h->hY, N, M, es, ldn));
+    CHK(hc.out_flat(dE, E, h->cve, (size_t)nobs * A * M * 8));
+    CHK(hc.out_flat(dit, iters, h->mit, (size_t)num_folds * A * 8));
     CHK(ensure(h, h->mcvidx, (size_t)nobs * 8));
     HIPCHK(h, hipMemcpyAsync(h->mcvidx.p, test_idx, (size_t)nobs * 8, hipMemcpyHostToDevice, h->stream));
     CHK(by_dtype(dtype, [&](auto t) {
@@ -935,63 +738,46 @@ int pls_hip_cv_folds_missing(pls_hip_handle h, const void *X, int64_t ldx, const
         return cv_folds_missing_device<Tx>(h, (const Tx *)dX, dldx, (const Tx *)dY, dldy, N, (int)K, (int)M, (int)A,
                                            (const long long *)h->mcvidx.p, (int)test_size, num_folds, dE, dit);
     }));
-    if (mem == PLS_HIP_MEM_HOST) {
-        HIPCHK(h, hipMemcpyAsync(E, dE, (size_t)nobs * A * M * 8, hipMemcpyDeviceToHost, h->stream));
-        if (iters) HIPCHK(h, hipMemcpyAsync(iters, dit, (size_t)num_folds * A * 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return PLS_HIP_OK;
+    return hc.finish();
 }
 
 int pls_hip_scores_missing(pls_hip_handle h, const void *X, int64_t ldx, int64_t N, int64_t K, int64_t A, const double *W, const double *P,
                            int dtype, int mem, void *S, int64_t lds) {
     CHK(check_handle(h));
-    if (dtype != PLS_HIP_F64 && dtype != PLS_HIP_F32) return fail(h, PLS_HIP_ERR_INVALID, "bad dtype");
-    if (mem != PLS_HIP_MEM_HOST && mem != PLS_HIP_MEM_DEVICE) return fail(h, PLS_HIP_ERR_INVALID, "bad mem kind");
+    CHK(check_dtype(h, dtype));
+    CHK(check_mem(h, mem));
     if (N < 1 || K < 1 || A < 1 || A > K || !X || !W || !P || !S || ldx < N || lds < N)
         return fail(h, PLS_HIP_ERR_INVALID, "bad scores_missing arguments: need N>=1, 1<=A<=K, ld>=N, X, W, P and S");
     if (K > (((i64)1 << 31) - 1)) return fail(h, PLS_HIP_ERR_UNSUPPORTED, "scores_missing: K < 2^31");
-    if (h->reducer || h->nranks > 1)
-        return fail(h, PLS_HIP_ERR_UNSUPPORTED, "scores_missing: not on a row-sharded handle");
+    CHK(check_unsharded(h, "scores_missing: not on a row-sharded handle"));
     CHK(set_device(h));
     const size_t es = esize(dtype);
     const void *dX = X;
     const double *dW = W, *dP = P;
     void *dS = S;
     i64 dldx = ldx, dlds = lds;
-    if (mem == PLS_HIP_MEM_HOST) {
-        const i64 ldn = N + ((-N) & 3);
-        CHK(ensure(h, h->hIn, (size_t)ldn * K * es));
-        CHK(ensure(h, h->hOut, (size_t)ldn * A * es));
-        CHK(ensure(h, h->hW, (size_t)K * A * 8));
-        CHK(ensure(h, h->hP, (size_t)K * A * 8));
-        CHK(h2d(h, h->hIn.p, ldn, X, ldx, N, K, es));
-        CHK(h2d(h, h->hW.p, K, W, K, K, A, 8));
-        CHK(h2d(h, h->hP.p, K, P, K, K, A, 8));
-        dX = h->hIn.p; dS = h->hOut.p; dW = (const double *)h->hW.p; dP = (const double *)h->hP.p;
-        dldx = dlds = ldn;
-    }
+    const i64 ldn = ld_quad(N);
+    HostCall hc(h, mem);
+    CHK(hc.in(dX, dldx, X, ldx, h->hIn, N, K, es, ldn));
+    CHK(hc.in(dW, W, h->hW, K, A));
+    CHK(hc.in(dP, P, h->hP, K, A));
+    CHK(hc.out(dS, dlds, S, lds, h->hOut, N, A, es, ldn));
     CHK(by_dtype(dtype, [&](auto t) {
         using Tx = decltype(t);
         return scores_missing_device<Tx>(h, (const Tx *)dX, dldx, N, (int)K, (int)A, dW, dP, (Tx *)dS, dlds);
     }));
-    if (mem == PLS_HIP_MEM_HOST) {
-        CHK(d2h(h, S, lds, dS, dlds, N, A, es));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return PLS_HIP_OK;
+    return hc.finish();
 }
 
 int pls_hip_colwise_z_scores_missing(pls_hip_handle h, const void *X, int64_t ldx, int64_t N, int64_t K, int dtype, int mem, void *Z,
                                      int64_t ldz, double *mean, double *sd, int64_t *nobs) {
     CHK(check_handle(h));
-    if (dtype != PLS_HIP_F64 && dtype != PLS_HIP_F32) return fail(h, PLS_HIP_ERR_INVALID, "bad dtype");
-    if (mem != PLS_HIP_MEM_HOST && mem != PLS_HIP_MEM_DEVICE) return fail(h, PLS_HIP_ERR_INVALID, "bad mem kind");
+    CHK(check_dtype(h, dtype));
+    CHK(check_mem(h, mem));
     if (N < 1 || K < 1 || !X || !mean || !sd || ldx < N || (Z && ldz < N))
         return fail(h, PLS_HIP_ERR_INVALID, "bad z_scores_missing arguments: need N>=1, K>=1, ld>=N, X, mean and sd");
     if (K > (((i64)1 << 31) - 1)) return fail(h, PLS_HIP_ERR_UNSUPPORTED, "z_scores_missing: K < 2^31");
-    if (h->reducer || h->nranks > 1)
-        return fail(h, PLS_HIP_ERR_UNSUPPORTED, "z_scores_missing: single rank only, not on a row-sharded handle");
+    CHK(check_unsharded(h, "z_scores_missing: single rank only, not on a row-sharded handle"));
     CHK(set_device(h));
     const size_t es = esize(dtype);
     const void *dX = X;
@@ -999,32 +785,28 @@ int pls_hip_colwise_z_scores_missing(pls_hip_handle h, const void *X, int64_t ld
     double *dmean = mean, *dsd = sd;
     long long *dn = (long long *)nobs;
     i64 dldx = ldx, dldz = ldz;
-    if (mem == PLS_HIP_MEM_HOST) {
-        CHK(ensure(h, h->hIn, (size_t)N * K * es));
-        CHK(ensure(h, h->mzo, (size_t)K * 3 * 8));  // [mean, sd, nobs]
-        CHK(h2d(h, h->hIn.p, N, X, ldx, N, K, es));
-        dX = h->hIn.p; dZ = Z ? h->hIn.p : nullptr;  // scaled in place in the staging copy
-        dmean = (double *)h->mzo.p; dsd = dmean + K; dn = nobs ? (long long *)(dsd + K) : nullptr;
-        dldx = dldz = N;
+    const size_t small = (size_t)K * 3 * 8;  // mzo = [mean, sd, nobs]
+    HostCall hc(h, mem);
+    CHK(hc.in(dX, dldx, X, ldx, h->hIn, N, K, es, ld_exact(N)));
+    if (hc.host) {  // scaled in place in the staging copy
+        dZ = Z ? const_cast<void *>(dX) : nullptr;
+        dldz = dldx;
+        CHK(hc.back(Z, ldz, dZ, dldz, N, K, es));
     }
+    CHK(hc.out(dmean, mean, h->mzo, K, 1, 8, small, 0));
+    CHK(hc.out(dsd, sd, h->mzo, K, 1, 8, small, (size_t)K * 8));
+    CHK(hc.out(dn, nobs, h->mzo, K, 1, 8, small, (size_t)K * 16));
     CHK(by_dtype(dtype, [&](auto t) {
         using Tx = decltype(t);
         return zscores_missing_device<Tx>(h, (const Tx *)dX, dldx, N, (int)K, (Tx *)dZ, dldz, dmean, dsd, dn);
     }));
-    if (mem == PLS_HIP_MEM_HOST) {
-        if (Z) CHK(d2h(h, Z, ldz, dZ, dldz, N, K, es));
-        CHK(d2h(h, mean, K, dmean, K, K, 1, 8));
-        CHK(d2h(h, sd, K, dsd, K, K, 1, 8));
-        if (nobs) CHK(d2h(h, nobs, K, dn, K, K, 1, 8));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return PLS_HIP_OK;
+    return hc.finish();
 }
 
 int pls_hip_synth_x(pls_hip_handle h, void *X, int64_t ldx, int64_t row0, int64_t nrows, int64_t K,
                     uint64_t seed, int dtype) {
     CHK(check_handle(h));
-    if (dtype != PLS_HIP_F64 && dtype != PLS_HIP_F32) return fail(h, PLS_HIP_ERR_INVALID, "bad dtype");
+    CHK(check_dtype(h, dtype));
     if (nrows < 0 || row0 < 0 || K < 1 || K > (1 << 28) || (nrows > 0 && !X) || ldx < std::max<i64>(nrows, 1))
         return fail(h, PLS_HIP_ERR_INVALID, "bad synth_x arguments");
     if (nrows == 0) return PLS_HIP_OK;
@@ -1049,7 +831,7 @@ int pls_hip_synth_x(pls_hip_handle h, void *X, int64_t ldx, int64_t row0, int64_
 int pls_hip_synth_y(pls_hip_handle h, void *Y, int64_t ldy, int64_t row0, int64_t nrows, int64_t M,
                     uint64_t seed, int dtype) {
     CHK(check_handle(h));
-    if (dtype != PLS_HIP_F64 && dtype != PLS_HIP_F32) return fail(h, PLS_HIP_ERR_INVALID, "bad dtype");
+    CHK(check_dtype(h, dtype));
     if (nrows < 0 || row0 < 0 || M < 1 || M > (1 << 20) || (nrows > 0 && !Y) || ldy < std::max<i64>(nrows, 1))
         return fail(h, PLS_HIP_ERR_INVALID, "bad synth_y arguments");
     if (nrows == 0) return PLS_HIP_OK;
@@ -1073,7 +855,3 @@ int pls_hip_synth_y(pls_hip_handle h, void *Y, int64_t ldy, int64_t row0, int64_
 }
 
 }  // extern "C"
-
-#include "xchg_ipc.hpp"
-
-#include "group_impl.hpp"
