@@ -158,7 +158,76 @@ PLAN_ROWS = [
     ("... not attached", fit(20000, 512, 1, 5, "f64", NIPALS, reducer=1), dict(xep_ok=0)),
 ]
 
-ROWS = NIPALS_ROWS + NIPALS_MORE + KERNEL_ROWS + PLAN_ROWS
+# ---- long leading dimensions: either side of every edge_level threshold ------------------------------------------------------------
+# The tile that reads the caller's matrix has CG = 8 / 16 / 32 column groups (K <= 128 / <= 256 / beyond) behind ONE descriptor
+# while CG ld es < 2^31 (fused_mode 1): 256 / 128 / 64 MiB per column.  From there on a descriptor per wave (CG / 8 groups:
+# fused_mode 2) while (CG / 8) ld es < 2^31: 2 GiB / 1 GiB / 512 MiB per column, then the tile-resident pass is out (fused_mode 0).
+# deflate_score_mode and wide_source_ok read with 32 groups, 4 per wave: one descriptor below 64 MiB (wide_mode 1), per wave
+# below 512 MiB (wide_mode 2), not addressable from 512 MiB on (wide_mode 0, no short-tile copy: the one-product kernels).
+MiB = 1 << 20
+LD_N = 5000
+ONE_DESCRIPTOR = {40: 256 * MiB, 200: 128 * MiB, 260: 64 * MiB}     # K -> bytes per column from which CG columns overflow 2^31
+PER_WAVE = {9: 2048 * MiB, 200: 1024 * MiB, 260: 512 * MiB}        # K -> bytes per column from which a wave's groups do
+
+
+def ld_at(nbytes, dt, below):
+    """the leading dimension (elements) of `nbytes` per column, or the last 16-byte aligned one below it"""
+    es = 8 if dt == "f64" else 4
+    return nbytes // es - (16 // es if below else 0)
+
+
+def _long_ld_rows():
+    rows = []
+    names = {KERNEL: "KERNEL", NIPALS: "NIPALS", GRAM: "GRAM", AUTO: "KERNEL"}   # (AUTO at 6 components of 5000 rows: KERNEL)
+    for dt in ("f64", "f32"):
+        for algo in (KERNEL, NIPALS, GRAM, AUTO):
+            for K, nbytes in ONE_DESCRIPTOR.items():
+                for below in (True, False):
+                    want = dict(algo=names[algo], fused_mode=1 if below else 2, wide_mode=0, tall_cg=8 if K <= 128 else 16 if K <= 256 else 32)
+                    if algo == NIPALS:   # the working copy is tiled on either side
+                        want.update(tiled_work=1, semi_fit=0, defer=1)
+                    rows.append((f"{names[algo]}/{algo} K={K} {dt} {'below' if below else 'at'} {nbytes // MiB} MiB",
+                                 fit(LD_N, K, 1, 6, dt, algo, ldx=ld_at(nbytes, dt, below)), want))
+            for K, nbytes in PER_WAVE.items():
+                for below in (True, False):
+                    want = dict(algo=names[algo], fused_mode=2 if below else 0, wide_mode=0)
+                    if algo == NIPALS:   # past the limit: a column-major copy for the one-product kernels
+                        want.update(tiled_work=int(below), semi_fit=0, wide_only=0, nip_copy=0, wide_cg=0)
+                        if not below:
+                            want.update(work=colmajor(LD_N, K, dt), ldw=pad(LD_N, dt))
+                    if algo == KERNEL:   # (6 components: below the 10 from which the copy of an aligned matrix pays)
+                        want.update(retile_fit=0, work=0)
+                    rows.append((f"{names[algo]}/{algo} K={K} {dt} {'below' if below else 'at'} {nbytes // MiB} MiB (per wave)",
+                                 fit(LD_N, K, 1, 6, dt, algo, ldx=ld_at(nbytes, dt, below)), want))
+        # 1024 < K <= 4096: fused_mode 0 at any ld; the semi-fused sweep and the short-tile copy follow wide_mode
+        for algo in (KERNEL, NIPALS):
+            for nbytes, lo, hi in ((64 * MiB, 1, 2), (512 * MiB, 2, 0)):
+                for below in (True, False):
+                    wm = lo if below else hi
+                    want = dict(fused_mode=0, wide_mode=wm, wide_cg=128 if wm else 0)
+                    want.update(dict(semi_fit=int(wm != 0), tiled_work=int(wm != 0), nip_copy=int(wm != 0)) if algo == NIPALS
+                                else dict(retile_fit=int(wm != 0)))
+                    rows.append((f"algo {algo} K=2048 {dt} {'below' if below else 'at'} {nbytes // MiB} MiB",
+                                 fit(LD_N, 2048, 1, 6, dt, algo, ldx=ld_at(nbytes, dt, below)), want))
+        # 4096 < K <= 8192 under NIPALS: wide_only needs wide_source_ok -- gone from 512 MiB per column on
+        for below in (True, False):
+            rows.append((f"wide_only K=6144 {dt} {'below' if below else 'at'} 512 MiB",
+                         fit(3000, 6144, 1, 3, dt, NIPALS, ldx=ld_at(512 * MiB, dt, below)),
+                         dict(fused_mode=0, wide_mode=0, wide_only=int(below), wide_cg=512 if below else 0, tiled_work=int(below))))
+    # the deferred write-back needs ONE descriptor for the 32 groups (fused_mode 1)
+    rows.append(("opt_defer=2 below 64 MiB", fit(4098, 512, 1, 6, "f64", NIPALS, defer=2, ldx=ld_at(64 * MiB, "f64", True)),
+                 dict(fused_mode=1, tall_cg=32, defer=2)))
+    rows.append(("opt_defer=2 at 64 MiB", fit(4098, 512, 1, 6, "f64", NIPALS, defer=2, ldx=ld_at(64 * MiB, "f64", False)),
+                 dict(fused_mode=2, tall_cg=32, defer=1)))
+    # AUTO with 40 components of 5000 x 260 fp64: 41 passes of 1.73 us + 40 x 14 us = 0.631 ms against SYRK 12.8 us + T 2.3 us +
+    # 40 x 13.7 us + 40 us = 0.602 ms -- GRAM, whatever the leading dimension is
+    rows.append(("AUTO A=40 at 64 MiB", fit(LD_N, 260, 1, 40, "f64", AUTO, ldx=ld_at(64 * MiB, "f64", False)), dict(algo="GRAM", fused_mode=2)))
+    return rows
+
+
+LONG_LD_ROWS = _long_ld_rows()
+
+ROWS = NIPALS_ROWS + NIPALS_MORE + KERNEL_ROWS + PLAN_ROWS + LONG_LD_ROWS
 
 
 @pytest.fixture(scope="module")

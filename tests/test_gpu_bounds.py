@@ -28,6 +28,18 @@ PREFILL = {8: 0x7FF4DEADBEEF0002, 4: 0x7FA5BEE2}
 LEAD_BYTES = 64
 TRAIL_BYTES = 4096
 
+# the bars of the step entry points below, by name: tests/test_gpu_long_ld.py holds the same calls to them at long leading dimensions
+XTY_BAR = 1e-13                        # of |X|^T |Y|, entry by entry
+DEFLATE_BAR_F64 = 1e-15                # of |src| + |t p^T|, cell by cell (fp32 storage: one ulp of the rounded reference)
+Z_BAR = {"f64": 1e-10, "f32": 5e-6}    # max |Z - Z_ref|
+SSE_BAR = 1e-10                        # of the largest entry of the reference
+CV_BAR = 1e-8                          # of max(max |E_ref|, 1)
+
+
+def xb_bar(dt, K):
+    """relative Frobenius error of X * Bm"""
+    return 2e-7 if dt == "f32" else 1e-14 * max(1.0, (K / 2000.0) ** 0.5)
+
 
 def _torch():
     import torch
@@ -275,7 +287,7 @@ def test_xb_writes_exactly_its_output(gpu, N, K, C, dt, xl, ol, xb4):
     ref = X[ri].cpu().numpy().astype(np.float64) @ Bh
     got = go[0][ri].cpu().numpy().astype(np.float64)
     err = np.linalg.norm(got - ref) / np.linalg.norm(ref)
-    assert err < (2e-7 if dt == "f32" else 1e-14 * max(1.0, (K / 2000.0) ** 0.5)), err
+    assert err < xb_bar(dt, K), err
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -316,7 +328,7 @@ def test_deflate_writes_exactly_dst(gpu, N, K, dt, layout, inplace):
     ref = s64 - np.outer(t64, p_h)
     got = gd[0].cpu().numpy()
     if dt == "f64":
-        assert (np.abs(got - ref) <= 1e-15 * (np.abs(s64) + np.abs(np.outer(t64, p_h)))).all()
+        assert (np.abs(got - ref) <= DEFLATE_BAR_F64 * (np.abs(s64) + np.abs(np.outer(t64, p_h)))).all()
     else:
         r32 = ref.astype(np.float32)
         assert (np.abs(got.astype(np.float64) - r32) <= np.spacing(np.abs(r32))).all()
@@ -357,7 +369,7 @@ def test_xty_writes_exactly_xy(gpu, N, K, M, dt, layout):
     X64, Y64 = Xh.astype(np.float64), Yh.astype(np.float64)
     ref = X64.T @ Y64
     scale = np.abs(X64).T @ np.abs(Y64)
-    assert (np.abs(go[0].cpu().numpy() - ref) <= 1e-13 * scale).all()
+    assert (np.abs(go[0].cpu().numpy() - ref) <= XTY_BAR * scale).all()
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -617,7 +629,7 @@ def test_z_scores_write_exactly_z_mean_sd(gpu, oracle, N, K, dt, layout, want_z)
     assert np.allclose(gs[1].cpu().numpy()[:, 0], sr.astype(np.float64), rtol=1e-12)
     if want_z:
         zr = ((xl - mr) / sr).astype(np.float64)
-        assert np.abs(gz[0].cpu().numpy().astype(np.float64) - zr).max() < (1e-10 if dt == "f64" else 5e-6)
+        assert np.abs(gz[0].cpu().numpy().astype(np.float64) - zr).max() < Z_BAR[dt]
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -660,7 +672,7 @@ def test_sse_by_components_writes_exactly_sse(gpu, N, A, M, dt, layout):
     gsx.assert_untouched(); gy.assert_untouched(); gq.assert_untouched()
     ins.check()
     ref = _sse_reference(Sh.astype(np.float64), Yh, Qh)
-    assert np.abs(go[0].cpu().numpy() - ref).max() < 1e-10 * np.abs(ref).max()
+    assert np.abs(go[0].cpu().numpy() - ref).max() < SSE_BAR * np.abs(ref).max()
 
 
 @pytest.mark.parametrize("mem", ["device", "host"])
@@ -693,7 +705,7 @@ def test_model_sse_writes_exactly_sse(gpu, oracle, mem):
     ins.check()
     ref = _sse_reference(Xh @ Rh, Yh, Qh)
     got = go[0] if dev == "numpy" else go[0].cpu().numpy()
-    assert np.abs(got - ref).max() < 1e-10 * np.abs(ref).max()
+    assert np.abs(got - ref).max() < SSE_BAR * np.abs(ref).max()
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -736,7 +748,7 @@ def test_cv_folds_write_exactly_e(gpu, oracle, name, N, K, M, A, ts, nf, env, me
     ref = _fold_reference(oracle, Xh, Yh, A, idx)                 # (M, nobs, A)
     want = ref.transpose(1, 0, 2).reshape(nobs, M * A)            # E[m (nobs A) + i + c nobs] = column m A + c, row i
     got = ge[0] if dev == "numpy" else ge[0].cpu().numpy()
-    assert np.abs(got - want).max() < 1e-8 * max(np.abs(ref).max(), 1.0)
+    assert np.abs(got - want).max() < CV_BAR * max(np.abs(ref).max(), 1.0)
 
 
 # ------------------------------------------------------------------------------------------------------------------------
