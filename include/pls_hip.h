@@ -550,8 +550,8 @@ PLS_HIP_API int pls_hip_cv_press_batch(pls_hip_handle h, const void *X, int64_t 
  * Per component the work copy is read three times and written once for M = 1 (deflate + w, t, p), read 2 iters + 1 times and
  * written once for M > 1; the first sweep reads the caller's matrix instead.  Workspace: the N x K work copy and, for short
  * wide X, up to 1024 partial score vectors.
- * Out of scope: row-sharded handles and groups, missing values in Y, resampling / x_diagnostics on data with NaN, a
- * sample-space form.  Cross-validation: pls_hip_cv_folds_missing below.
+ * Out of scope: row-sharded handles and groups, missing values in Y, resampling on data with NaN, a sample-space form.
+ * Cross-validation: pls_hip_cv_folds_missing below; Q residuals, T^2 and R^2 X: pls_hip_x_diagnostics_missing below.
  */
 PLS_HIP_API int pls_hip_fit_missing(pls_hip_handle h, const void *X, int64_t ldx, const void *Y, int64_t ldy,
                                     int64_t N, int64_t K, int64_t M, int64_t A, int dtype, int mem, double *W, double *P,
@@ -564,6 +564,50 @@ PLS_HIP_API int pls_hip_fit_missing(pls_hip_handle h, const void *X, int64_t ldx
  * handle with a reducer installed: PLS_HIP_ERR_UNSUPPORTED.  PLS_HIP_MEM_DEVICE: the call only enqueues. */
 PLS_HIP_API int pls_hip_scores_missing(pls_hip_handle h, const void *X, int64_t ldx, int64_t N, int64_t K, int64_t A,
                                        const double *W, const double *P, int dtype, int mem, void *S, int64_t lds);
+
+/* X-space diagnostics of rows, new or training, that may have missing cells: what pls_hip_x_diagnostics is to complete data, for
+ * the models of pls_hip_fit_missing.  NaN in X marks a missing cell exactly as for pls_hip_fit_missing: any payload, either sign,
+ * and the bits of the result do not depend on it.  W and P are the model's own W and P (K x A, ld K, fp64) -- NOT R: the
+ * convention of pls_hip_scores_missing.  For row i let x be the row and O the set of its observed columns:
+ *   q_0 = sum_{k in O} x_k^2
+ *   for a = 0 .. A-1:
+ *     t_a = sum_{k in O} x_k W[k,a] / sum_{k in O} W[k,a]^2        (a denominator of exactly 0 gives 0)
+ *     x_k <- x_k - t_a P[k,a]  for k in O                          (a NaN stays a NaN)
+ *     q_{a+1} = sum_{k in O} x_k^2
+ * Outputs; any of them may be NULL, and work nobody asked for is not done:
+ *   S     N x A, ld lds, storage dtype   S[i,a] = t_a: the definition of pls_hip_scores_missing
+ *   Qres  N x A, ld ldq, fp64            Qres[i,c-1] = q_c: the Q residual over the observed cells after c components
+ *   T2    N x A, ld ldt2, fp64           T2[i,c-1] = sum_{a<c} t_a^2 / tvar[a]
+ *   ssx   A + 1, fp64                    ssx[0] = sum_i q_0, ssx[c] = sum_i Qres[i,c-1]; R^2 X_c = 1 - ssx[c] / ssx[0], over the
+ *                                        observed cells
+ *   sst   A, fp64                        sst[a] = sum_i t_a^2
+ *   nobs  N, int64                       the observed cells of row i, so that a caller can scale Q by K / nobs
+ * tvar == NULL means X is the training set: tvar[a] = sst[a] / (N - 1) from this call's own scores.  A zero or non-finite tvar[a]
+ * gives inf / NaN in T2 from column a on, as in pls_hip_x_diagnostics.  A row without an observed cell has S = Qres = T2 = 0 and
+ * nobs = 0.
+ * All arithmetic is fp64.  The row is NEVER rounded to the storage type between components, and T2, Qres, ssx and sst use the
+ * unrounded t_a.  This differs from pls_hip_scores_missing, which keeps its work copy in the storage type: with fp32 storage the
+ * two calls' S agree to fp32 rounding, with fp64 storage to 1e-10.
+ * Sums run in a fixed order with no atomics.  An output has the same bits whichever other outputs are asked for.  Two calls with
+ * the same arguments return the same bits, from host or device memory (a host-memory call is the device-memory call on the
+ * staged layout), whatever the handle ran before ("History" at the top of this file).  As for every entry point, the bits may
+ * differ with the alignment of X: 16-byte loads are used when the pointer and ldx allow them, element loads otherwise.
+ * Two routes, chosen by shape (xdiagmiss_layout.hpp), both reading the caller's X directly, neither with a work copy.  Tall X
+ * (K <= 1024, N >= 8 rows per compute unit): a workgroup holds a tile of rows on chip across all components, X is read ONCE.
+ * Everything else: one read-only sweep per component plus one for q_A (A + 1 reads of X; A when neither Qres nor ssx is asked
+ * for), every cell rebuilt in registers from the scores so far, K split over workgroups where the rows alone do not fill the
+ * chip.  PLS_HIP_XDIAGMISS_ROUTE=stream in the environment of pls_hip_create forces the second route (the cross-check; the two
+ * agree to rounding, not in bits).  Workspace: N x A scores, up to N x (A + 1) Q columns, and on the streaming route 32 bytes per
+ * row and K range -- nothing N x K.
+ * `mem` says where X, W, P, tvar and every output live.  PLS_HIP_MEM_DEVICE: the call only enqueues.
+ * PLS_HIP_ERR_INVALID, before anything is written: N < 1; A < 1 or A > K; ldx < N, or the ld of an output that was asked for < N;
+ * X, W or P NULL; T2 asked for with tvar == NULL and N < 2.  PLS_HIP_ERR_UNSUPPORTED, before anything is written: a handle with a
+ * reducer installed (and K >= 2^31, A > 2^20).  PLS_HIP_OPT_ALGO, _FUSE, _DEFER and _GRAPH do not apply.
+ * Out of scope: row-sharded handles and groups, NaN in W, P or tvar, a per-column R^2 X. */
+PLS_HIP_API int pls_hip_x_diagnostics_missing(pls_hip_handle h, const void *X, int64_t ldx, int64_t N, int64_t K, int64_t A,
+                                              const double *W, const double *P, const double *tvar, int dtype, int mem,
+                                              double *Qres, int64_t ldq, double *T2, int64_t ldt2, void *S, int64_t lds,
+                                              double *ssx, double *sst, int64_t *nobs);
 
 /* Cross-validation folds of X with missing values: what pls_hip_cv_folds is to pls_hip_fit, for pls_hip_fit_missing.
  * Fold f holds out the rows test_idx[f * test_size .. + test_size) (host memory, as in pls_hip_cv_folds).  Its result is BY

@@ -87,6 +87,8 @@ PROTOTYPES = [
                                    _vp, _vp]),
     ("pls_hip_cv_folds_missing", _int, [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _int, _int, _vp, _vp]),
     ("pls_hip_scores_missing", _int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _int, _int, _vp, _i64]),
+    ("pls_hip_x_diagnostics_missing", _int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _int, _int, _vp, _i64, _vp, _i64,
+                                             _vp, _i64, _vp, _vp, _vp]),
     ("pls_hip_colwise_z_scores_missing", _int, [_vp, _vp, _i64, _i64, _i64, _int, _int, _vp, _i64, _vp, _vp, _vp]),
     ("pls_hip_synth_x", _int, [_vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_uint64, _int]),
     ("pls_hip_synth_y", _int, [_vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_uint64, _int]),

@@ -41,6 +41,7 @@ struct pls_hip_context {
     DevBuf rsw, rsB, rsacc, rsX, rsY, rsW, rsoS;  // pls_hip_fit_resampled (plan_resample.hpp): the state of a round's replicates (general route: of one fit), a round's B, [s1, s2, B0], the row-scaled work copies, host staging of the weights and of [B0, Bmean, Bm2]
     DevBuf mX, mws, mit, mzo;  // pls_hip_fit_missing and its companions (plan_missing.hpp): the work copy of X, vectors and partials, host staging of iters and of [mean, sd, nobs]
     DevBuf mcv, mcvidx;  // pls_hip_cv_folds_missing (plan_missing_cv.hpp): the slabs of a round's folds (miss_layout.hpp) and the round's word, the test rows (iters are staged in mit)
+    DevBuf xmws, xmon;  // pls_hip_x_diagnostics_missing (plan_xdiag_missing.hpp): scores, Q columns, range partials and slices (xdiagmiss_layout.hpp), host staging of nobs
     i64 opt_missing_iters = 500;  // PLS_HIP_OPT_MISSING_ITERS
     int *mconv_host = nullptr;    // pinned: where the host reads the convergence word of the M > 1 loop
     i64 opt_val_lds_rows = -1;  // PLS_HIP_OPT_VALIDATION_LDS_ROWS; -1 = the device's own limit
@@ -109,6 +110,8 @@ struct pls_hip_context {
     //   PLS_HIP_DUALCVB_ROUND=n  at most n (problem, fold) pairs per round of pls_hip_cv_press_batch under PLS_HIP_ALGO_DUAL
     //                            (tests: several rounds)
     //   PLS_HIP_MISSCV_ROUND=n   at most n folds per round of pls_hip_cv_folds_missing (tests: several rounds)
+    //   PLS_HIP_XDIAGMISS_ROUTE=stream  pls_hip_x_diagnostics_missing on its streaming route whatever the shape (the cross-check of
+    //                            the row-resident route; tests compare)
     //   PLS_HIP_RESIDENT=0       mid-size single-response fits on the general plan instead of the one-launch resident fit
     //   PLS_HIP_REPLICA_GUARD=0  no replica-divergence check after a sharded fit (must be the same on every rank)
     //   PLS_HIP_TURNAROUND=0     every fused pass walks ascending with the nt policy throughout (A/B measurements; must be the
@@ -126,6 +129,7 @@ struct pls_hip_context {
         bool cvbatch_refit = false;
         i64 dualcvb_round = 0;
         i64 misscv_round = 0;
+        bool xdiagmiss_stream = false;
         bool tiny = true, cv_refit = false, tail = true, replica_guard = true, resident = true;
         int tail_update = 1;  // 0: never, 1: in the tail of READ-ONLY passes (default), 2: of every pass
         int xb4 = 1;          // PLS_HIP_XB4=0: X B with 5..32 columns on the older kernels
@@ -147,6 +151,7 @@ struct pls_hip_context {
         env.cvbatch_refit = on("PLS_HIP_CVBATCH_REFIT");
         num("PLS_HIP_DUALCVB_ROUND", env.dualcvb_round);
         num("PLS_HIP_MISSCV_ROUND", env.misscv_round);
+        if (const char *e = getenv("PLS_HIP_XDIAGMISS_ROUTE")) env.xdiagmiss_stream = std::strcmp(e, "stream") == 0;
         env.tail = !off("PLS_HIP_TAIL");
         const char *tail = getenv("PLS_HIP_TAIL");
         env.tail_update = tail ? (atoi(tail) >= 2 ? 2 : 0) : 1;
@@ -195,6 +200,7 @@ struct pls_hip_context {
     SCRATCH(dcvb) SCRATCH(cvbpos) SCRATCH(cvbidx) SCRATCH(cvbo) SCRATCH(cvboE)                                                         \
     SCRATCH(rsw) SCRATCH(rsB) SCRATCH(rsacc) SCRATCH(rsX) SCRATCH(rsY) SCRATCH(rsW) SCRATCH(rsoS)                                      \
     SCRATCH(mX) SCRATCH(mws) SCRATCH(mit) SCRATCH(mzo) SCRATCH(mcv) SCRATCH(mcvidx)                                                    \
+    SCRATCH(xmws) SCRATCH(xmon)                                                                                                        \
     SCRATCH(guard)
 
 namespace {

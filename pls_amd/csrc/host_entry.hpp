@@ -94,6 +94,7 @@ i64 ld_exact(i64 n) { return n; }                                         // pac
 //   pls_hip_fit_missing        quad   hX hY                              hW hP hR hQ hB hT mit                       no
 //   pls_hip_cv_folds_missing   quad   hX hY                              cve mit (flat)                              no (its plan synchronises for either memory)
 //   pls_hip_scores_missing     quad   hIn hW hP                          hOut                                        no
+//   pls_hip_x_diagnostics_missing  quad  hIn hW hP xdsmall[tvar]      xdoQ xdoT xdoS xdsmall[ssx | sst] xmon      no
 //   pls_hip_colwise_z_scores_missing  exact  hIn                         hIn (Z, in place) mzo[mean | sd | nobs]     no
 //
 // guard = check_diverged() behind the synchronisation.  The index list of the cv entries is the caller's host memory for either

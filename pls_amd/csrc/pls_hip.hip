@@ -42,6 +42,7 @@
 #include "synth_kernels.hpp"
 #include "missing_kernels.hpp"
 #include "missing_cv_kernels.hpp"
+#include "xdiag_missing_kernels.hpp"
 #include "host_pipeline.hpp"
 #include "exchange_kernels.hpp"
 
@@ -69,6 +70,7 @@ using plsk::i64;
 #include "plan_dual_cvbatch.hpp"
 #include "plan_missing.hpp"
 #include "plan_missing_cv.hpp"
+#include "plan_xdiag_missing.hpp"
 #include "xchg_ipc.hpp"
 #include "group_impl.hpp"
 
@@ -765,6 +767,47 @@ int pls_hip_scores_missing(pls_hip_handle h, const void *X, int64_t ldx, int64_t
     CHK(by_dtype(dtype, [&](auto t) {
         using Tx = decltype(t);
         return scores_missing_device<Tx>(h, (const Tx *)dX, dldx, N, (int)K, (int)A, dW, dP, (Tx *)dS, dlds);
+    }));
+    return hc.finish();
+}
+
+int pls_hip_x_diagnostics_missing(pls_hip_handle h, const void *X, int64_t ldx, int64_t N, int64_t K, int64_t A, const double *W,
+                                  const double *P, const double *tvar, int dtype, int mem, double *Qres, int64_t ldq, double *T2,
+                                  int64_t ldt2, void *S, int64_t lds, double *ssx, double *sst, int64_t *nobs) {
+    CHK(check_handle(h));
+    CHK(check_dtype(h, dtype));
+    CHK(check_mem(h, mem));
+    if (N < 1 || K < 1 || A < 1 || A > K || !X || !W || !P || ldx < N || (Qres && ldq < N) || (T2 && ldt2 < N) || (S && lds < N))
+        return fail(h, PLS_HIP_ERR_INVALID, "bad x_diagnostics_missing arguments: need N>=1, 1<=A<=K, ld>=N, X, W and P");
+    if (T2 && !tvar && N < 2)
+        return fail(h, PLS_HIP_ERR_INVALID, "x_diagnostics_missing: T2 from the call's own scores needs N >= 2");
+    if (K > (((i64)1 << 31) - 1) || A > (1 << 20)) return fail(h, PLS_HIP_ERR_UNSUPPORTED, "x_diagnostics_missing: K < 2^31, A <= 2^20");
+    CHK(check_unsharded(h, "x_diagnostics_missing: not on a row-sharded handle"));
+    CHK(set_device(h));
+    const size_t es = esize(dtype);
+    const void *dX = X;
+    const double *dW = W, *dP = P, *dtv = tvar;
+    double *dQ = Qres, *dT2 = T2, *dssx = ssx, *dsst = sst;
+    void *dS = S;
+    long long *dn = (long long *)nobs;
+    i64 dldx = ldx, dldq = ldq, dldt2 = ldt2, dlds = lds;
+    const i64 ldn = ld_quad(N);
+    const size_t small = (size_t)(3 * A + 1) * 8;  // xdsmall = [tvar (A), ssx (A + 1), sst (A)]
+    HostCall hc(h, mem);
+    CHK(hc.in(dX, dldx, X, ldx, h->hIn, N, K, es, ldn));
+    CHK(hc.in(dW, W, h->hW, K, A));
+    CHK(hc.in(dP, P, h->hP, K, A));
+    if (tvar) CHK(hc.in(dtv, tvar, h->xdsmall, A, 1, 8, small, 0));
+    CHK(hc.out(dQ, dldq, Qres, ldq, h->xdoQ, N, A, 8, ldn));
+    CHK(hc.out(dT2, dldt2, T2, ldt2, h->xdoT, N, A, 8, ldn));
+    CHK(hc.out(dS, dlds, S, lds, h->xdoS, N, A, es, ldn));
+    CHK(hc.out(dssx, ssx, h->xdsmall, A + 1, 1, 8, small, (size_t)A * 8));
+    CHK(hc.out(dsst, sst, h->xdsmall, A, 1, 8, small, (size_t)(2 * A + 1) * 8));
+    CHK(hc.out(dn, nobs, h->xmon, N, 1));
+    CHK(by_dtype(dtype, [&](auto t) {
+        using Tx = decltype(t);
+        return xdiag_missing_device<Tx>(h, (const Tx *)dX, dldx, N, (int)K, (int)A, dW, dP, dtv, dQ, dldq, dT2, dldt2, (Tx *)dS, dlds, dssx,
+                                        dsst, dn);
     }));
     return hc.finish();
 }

@@ -750,6 +750,62 @@ class Handle:
         L.check(rc, self.h)
         return S
 
+    def x_diagnostics_missing(self, X, W, P, tvar=None, want=("Q", "T2", "ssx")):
+        """X-space diagnostics of rows, new or training, that may have missing cells (pls_hip_x_diagnostics_missing): NaN in X
+        marks a missing cell, W and P (K, A) are the model's own W and P as for scores_missing.  `want` picks from "Q" (Q
+        residuals over the observed cells, N x A), "T2" (Hotelling T^2, N x A), "S" (scores, N x A in the dtype of X), "ssx"
+        (A + 1: the sum of the observed x^2, then the sums of the Q columns), "sst" (A: column sums of squares of the scores),
+        "nobs" (N, int64: observed cells per row); the result is a dict of those.  tvar (A) = t_a^T t_a / (n_train - 1) of the
+        training scores; None means X IS the training data.  Torch CUDA tensors stay on the device, numpy arrays take the
+        library's host path."""
+        want = set(want)
+        bad = want - {"Q", "T2", "S", "ssx", "sst", "nobs"}
+        if bad:
+            raise L.PlsHipError(L.ERR_INVALID, f"x_diagnostics_missing: unknown output(s) {sorted(bad)}")
+        if _is_torch(X):
+            X = as_colmajor(X)
+            N, K = X.shape
+            dev, f64 = X.device, torch.float64
+            A = W.shape[1]
+            Wc = colmajor_empty(K, A, f64, dev, ld=K).copy_(W)
+            Pc = colmajor_empty(K, A, f64, dev, ld=K).copy_(P)
+            tv = None if tvar is None else torch.as_tensor(tvar, dtype=f64, device=dev).contiguous()
+            out = {}
+            if "Q" in want: out["Q"] = colmajor_empty(N, A, f64, dev)
+            if "T2" in want: out["T2"] = colmajor_empty(N, A, f64, dev)
+            if "S" in want: out["S"] = colmajor_empty(N, A, X.dtype, dev)
+            if "ssx" in want: out["ssx"] = torch.empty(A + 1, dtype=f64, device=dev)
+            if "sst" in want: out["sst"] = torch.empty(A, dtype=f64, device=dev)
+            if "nobs" in want: out["nobs"] = torch.empty(N, dtype=torch.int64, device=dev)
+            ptr = lambda k: out[k].data_ptr() if k in out else None
+            ldo = lambda k: _ld(out[k]) if k in out else 1
+            rc = self._lib.pls_hip_x_diagnostics_missing(self.h, X.data_ptr() or None, _ld(X), N, K, A, Wc.data_ptr(), Pc.data_ptr(),
+                                                         tv.data_ptr() if tv is not None else None, self._dt(X), L.MEM_DEVICE,
+                                                         ptr("Q"), ldo("Q"), ptr("T2"), ldo("T2"), ptr("S"), ldo("S"), ptr("ssx"),
+                                                         ptr("sst"), ptr("nobs"))
+            L.check(rc, self.h)
+            self._last_inputs = (X, Wc, Pc, tv)
+            return out
+        dt = np.float32 if np.asarray(X).dtype == np.float32 else np.float64
+        X = _np_f(X, dt); W = _np_f(W, np.float64); P = _np_f(P, np.float64)
+        N, K = X.shape
+        A = W.shape[1]
+        tv = None if tvar is None else np.ascontiguousarray(tvar, dtype=np.float64)
+        out = {}
+        if "Q" in want: out["Q"] = np.zeros((N, A), order="F")
+        if "T2" in want: out["T2"] = np.zeros((N, A), order="F")
+        if "S" in want: out["S"] = np.zeros((N, A), dtype=dt, order="F")
+        if "ssx" in want: out["ssx"] = np.zeros(A + 1)
+        if "sst" in want: out["sst"] = np.zeros(A)
+        if "nobs" in want: out["nobs"] = np.zeros(N, dtype=np.int64)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        ptr = lambda k: p(out[k]) if k in out else None
+        rc = self._lib.pls_hip_x_diagnostics_missing(self.h, p(X), max(N, 1), N, K, A, p(W), p(P), p(tv) if tv is not None else None,
+                                                     L.F64 if dt == np.float64 else L.F32, L.MEM_HOST, ptr("Q"), max(N, 1),
+                                                     ptr("T2"), max(N, 1), ptr("S"), max(N, 1), ptr("ssx"), ptr("sst"), ptr("nobs"))
+        L.check(rc, self.h)
+        return out
+
     def z_scores_missing(self, X, inplace: bool = False):
         """(Z, mean, sd, nobs) over the observed cells of each column (pls_hip_colwise_z_scores_missing): sd with nobs - 1,
         NaN kept in Z.  A column with fewer than two observed cells, or a constant one, is NaN throughout."""
@@ -1249,11 +1305,21 @@ class Model:
         """dict(Q, T2: N x A; R2X: A) for 1..A components: the Q residual (squared distance of a row from the model plane),
         Hotelling's T^2 (its distance from the centre inside the plane, scaled by the variance of the TRAINING scores) and
         the share of sum X^2 the components reproduce.  X_new=None: the training data.  New rows must be preprocessed as
-        the training data was (the model does no centring of its own)."""
+        the training data was (the model does no centring of its own).  A model fitted with missing=True / plsr_missing takes
+        NaN in X for missing cells (Handle.x_diagnostics_missing with the model's W and P): Q and R2X are then over the observed
+        cells, and the dict has "nobs", the observed cells of each row, as well."""
         X = self._X if X_new is None else X_new
         tv = self._tvar()
         if _is_torch(X) != _is_torch(tv):
             tv = tv.cpu().numpy() if _is_torch(tv) else torch.as_tensor(tv, device=X.device)
+        if self._missing:
+            W, P = self.W, self.P
+            if _is_torch(X) != _is_torch(W):
+                W, P = ((W.cpu().numpy(), P.cpu().numpy()) if _is_torch(W) else
+                        (torch.as_tensor(np.asarray(W), device=X.device), torch.as_tensor(np.asarray(P), device=X.device)))
+            out = self.handle.x_diagnostics_missing(X, W, P, tvar=tv, want=("Q", "T2", "ssx", "nobs"))
+            ssx = out["ssx"]
+            return dict(Q=out["Q"], T2=out["T2"], R2X=1.0 - ssx[1:] / ssx[0], nobs=out["nobs"])
         R, P = self.R, self.P
         if _is_torch(X) != _is_torch(R):
             R, P = ((R.cpu().numpy(), P.cpu().numpy()) if _is_torch(R) else
