@@ -1,5 +1,6 @@
 // miss_layout.hpp -- the sweep geometry of the missing-value plans and the workspace slab of a fold of
-// pls_hip_cv_folds_missing: miss_geom_of, a pure function of (N, K, element size, CU count), and MissCvLayout, the byte offsets
+// pls_hip_cv_folds_missing: miss_row_split, the K split of every row sweep of the family (the diagnostics' streaming route
+// included), miss_geom_of, a pure function of (N, K, element size, CU count), and MissCvLayout, the byte offsets
 // of a fold's fields and the fold's byte count.  The same MissCvLayout sizes the round (plan_missing_cv.hpp) and is handed to
 // the kernels that carve the slab (missing_cv_kernels.hpp).  Plain C++17, no HIP and no handle: tests/cpp/missing_cv_layout.cpp
 // builds it with the host compiler alone.
@@ -8,7 +9,8 @@
 
 namespace plsk {
 
-constexpr int MISS_KC = 8;  // columns per workgroup of the column sweep: 2 x 8 fp64 accumulators per lane
+constexpr int MISS_KC = 8;        // columns per workgroup of the column sweep: 2 x 8 fp64 accumulators per lane
+constexpr int MISS_RF_ROWS = 16;  // rows per workgroup of the kernels that add the K ranges of a row sweep (miss_ranges_sum)
 
 // geometry of the three sweeps of one call; the work copy has 16-byte columns (ldw a multiple of 16 / element size)
 struct MissGeom {
@@ -22,6 +24,31 @@ struct MissGeom {
     i64 nbK, nbN;  // blocks of the K- and N-parallel kernels
 };
 
+// The split of a row sweep (miss_row_walk of missing_kernels.hpp): a lane owns `vec` rows, a workgroup is RL = 1 << lrl row
+// lanes x CL = WG / RL column lanes, and K is cut into S ranges of kper columns (a multiple of CL) where the nrb row blocks
+// alone do not fill the chip.  The one copy of the rule: miss_geom_of and xdiagmiss_geom_of (xdiagmiss_layout.hpp) call it.
+struct MissRowSplit {
+    int lrl;      // log2 of the row lanes of a workgroup
+    i64 nrb;      // row blocks
+    int S, kper;  // K ranges (1: no partials) and the columns of one
+};
+
+inline MissRowSplit miss_row_split(i64 N, i64 K, int vec, int num_cu) {
+    MissRowSplit s;
+    const i64 nv = (N + vec - 1) / vec;
+    s.lrl = 0;
+    while ((1 << s.lrl) < WG && ((i64)1 << s.lrl) < nv) ++s.lrl;
+    const int RL = 1 << s.lrl, CL = WG >> s.lrl;
+    s.nrb = (nv + RL - 1) / RL;
+    const i64 smax = std::max<i64>(1, K / (8 * CL));  // at least 8 columns per lane of a range
+    const i64 S = std::min<i64>(std::min<i64>(std::max<i64>(1, (4 * (i64)num_cu) / s.nrb), smax), 65535);
+    i64 kper = (K + S - 1) / S;
+    kper += (-kper) & (CL - 1);
+    s.kper = (int)std::min<i64>(kper, ((i64)1 << 31) - 1);
+    s.S = (int)((K + s.kper - 1) / s.kper);
+    return s;
+}
+
 inline MissGeom miss_geom_of(i64 N, i64 K, int es, int num_cu) {
     const int FV = 16 / es;
     MissGeom g;
@@ -31,17 +58,11 @@ inline MissGeom miss_geom_of(i64 N, i64 K, int es, int num_cu) {
     const i64 nch = (N + WG - 1) / WG;
     // 5 workgroups per CU are resident at the 89 VGPRs of the deflating sweep: all of them in one round, no tail
     g.G = (int)std::min<i64>(std::min<i64>(std::max<i64>(1, (5 * (i64)num_cu) / g.nkg), nch), 65535);
-    const i64 nv = (N + FV - 1) / FV;
-    g.lrl = 0;
-    while ((1 << g.lrl) < WG && ((i64)1 << g.lrl) < nv) ++g.lrl;
-    const int RL = 1 << g.lrl, CL = WG >> g.lrl;
-    g.nrb = (nv + RL - 1) / RL;
-    const i64 smax = std::max<i64>(1, K / (8 * CL));  // at least 8 columns per lane of a range
-    i64 S = std::min<i64>(std::min<i64>(std::max<i64>(1, (4 * (i64)num_cu) / g.nrb), smax), 65535);
-    i64 kper = (K + S - 1) / S;
-    kper += (-kper) & (CL - 1);
-    g.kper = (int)std::min<i64>(kper, ((i64)1 << 31) - 1);
-    g.S = (int)((K + g.kper - 1) / g.kper);
+    const MissRowSplit s = miss_row_split(N, K, FV, num_cu);
+    g.lrl = s.lrl;
+    g.nrb = s.nrb;
+    g.S = s.S;
+    g.kper = s.kper;
     g.GY = (int)std::min<i64>(nch, 2 * (i64)num_cu);
     g.nbK = (K + WG - 1) / WG;
     g.nbN = nch;

@@ -4,7 +4,10 @@
 //                            template deflates on the way (x - t_prev[i] p_prev[k] in registers, stored to the work copy)
 //   miss_row_kernel          num[i], den[i] = sum over the observed columns of row i of x w_k, w_k^2 (t from w); tall X in one
 //                            pass, short wide X split over K with partials and miss_row_finish_kernel
-//   the small kernels        normalisation of w, q, t^T t, the convergence word, u = Y q / q^T q, the deflation of Y, the R recursion
+//   the row sweep's parts    miss_obs_xw / miss_obs_xx (the observed-cell steps), miss_load_rows, miss_row_walk<T, V, U, NACC>
+//                            with a cell policy, miss_lanes_meet, miss_ranges_sum: written once, for this file's row sweep and
+//                            for the streaming sweep of xdiag_missing_kernels.hpp
+//   the small kernels       normalisation of w, q, t^T t, the convergence word, u = Y q / q^T q, the deflation of Y, the R recursion
 //   miss_colmoments_kernel   count, mean, M2 of the observed cells of a column in one sweep; miss_zscale_kernel scales
 // All sums fp64 and in a fixed order, no atomics; a quotient whose denominator is exactly 0 (no observed cell) is 0.  The mask
 // test is x == x: the library is built without -ffast-math, with it the test would be compiled away.
@@ -13,13 +16,28 @@
 // __global__ wrapper each: missing_cv_kernels.hpp wraps the same bodies once more, with the fold of a round in blockIdx.z.
 #pragma once
 #include "common.hpp"
-#include "miss_layout.hpp"  // MISS_KC, the sweep geometry
+#include "miss_layout.hpp"  // MISS_KC, MISS_RF_ROWS, the sweep geometry
 
 namespace plsk {
 
 constexpr int MISS_MAX_M = 32;  // responses the entry point takes
 
 __device__ __forceinline__ double miss_quot(double num, double den) { return den == 0.0 ? 0.0 : num / den; }
+
+// The observed-cell steps, the only places the mask test of a sweep is written: a NaN cell leaves the sums as they are.
+//   num += x w, den += w^2 (w: the factor the cell is multiplied with)
+__device__ __forceinline__ void miss_obs_xw(double x, double w, double &num, double &den) {
+    const bool ob = x == x;
+    num = ob ? fma(x, w, num) : num;
+    den = ob ? fma(w, w, den) : den;
+}
+//   q += x^2, cnt += 1 (a double on the streaming route, an int in the resident tile)
+template <typename C>
+__device__ __forceinline__ void miss_obs_xx(double x, double &q, C &cnt) {
+    const bool ob = x == x;
+    q = ob ? fma(x, x, q) : q;
+    cnt = ob ? cnt + 1 : cnt;
+}
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // Column sweep.  grid = (column groups ceil(K / MISS_KC), row groups G): the layout of xty_kernel with the two grid dimensions
@@ -65,11 +83,7 @@ __device__ __forceinline__ void miss_col_body(const T *src, i64 lds_, T *dst, i6
                     for (int j = 0; j < V; ++j) {
                         double xd = (double)x[kc].v[j];
                         if (DEFL) xd = fma(-tv[j], pk[kc], xd);
-                        if (ACC) {
-                            const bool ob = xd == xd;
-                            an[kc] = ob ? fma(xd, vv[j], an[kc]) : an[kc];
-                            ad[kc] = ob ? fma(vv[j], vv[j], ad[kc]) : ad[kc];
-                        }
+                        if (ACC) miss_obs_xw(xd, vv[j], an[kc], ad[kc]);
                         x[kc].v[j] = (T)xd;
                     }
                     if (STORE) st_pack_nt<T, V>(dst + i0 + (k0 + kc) * ldd, x[kc]);
@@ -85,11 +99,7 @@ __device__ __forceinline__ void miss_col_body(const T *src, i64 lds_, T *dst, i6
                         if (kc < kn) {
                             double xd = (double)src[i0 + j + (k0 + kc) * lds_];
                             if (DEFL) xd = fma(-tj, pk[kc], xd);
-                            if (ACC) {
-                                const bool ob = xd == xd;
-                                an[kc] = ob ? fma(xd, vj, an[kc]) : an[kc];
-                                ad[kc] = ob ? fma(vj, vj, ad[kc]) : ad[kc];
-                            }
+                            if (ACC) miss_obs_xw(xd, vj, an[kc], ad[kc]);
                             if (STORE) dst[i0 + j + (k0 + kc) * ldd] = (T)xd;
                         }
                 }
@@ -164,87 +174,129 @@ __global__ __launch_bounds__(WG) void miss_normalize_kernel(double *__restrict__
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
-// Row sweep over the work copy (16-byte columns: ldx a multiple of V; the padding rows are read and never used).
+// Row sweep, shared by the fit, the folds (over the work copy) and the streaming diagnostics (over the caller's X).
 // The workgroup is RL = 1 << lrl row lanes x CL = WG / RL column lanes: lane (r, c) owns the V rows (blockIdx.x RL + r) V ... and
-// walks the columns kb + c, kb + c + CL, ... of the K range blockIdx.y; the column lanes meet in LDS in the order of c.
+// walks the columns kb + c, kb + c + CL, ... of the K range blockIdx.y (miss_row_split), U columns in flight per batch, then a
+// tail; the column lanes of a row meet in LDS in the order of c.  A cell policy says what the factor of column k is and what
+// happens to the cells of a batch between their load and their accumulation.
+//   acc[0], acc[1]   num, den = sum over the observed columns of x w_k, w_k^2
+//   acc[2], acc[3]   NACC = 4 only: sum of x^2, observed cells
+//   PADDED           the work copy (16-byte columns: ldx a multiple of V): every lane loads whole packs, the padding rows are
+//                    read and never used.  Else rows beyond N are never read: the lanes are split ONCE into those whose V rows
+//                    all exist and those of the one pack that straddles row N.  (A guard per load, or the split on the work copy
+//                    too, costs the fit's sweep its 8 waves per SIMD: profiles/missing_rows/resources.md.)
+// ------------------------------------------------------------------------------------------------------------------------------
+// V rows i .. i + V - 1 of one column as fp64; whole = (i + V <= N): one pack, else element by element -- rows beyond N are 0,
+// never used and never read.  The row sweep passes `whole` as a constant (it splits its lanes once), so its loops test nothing
+// per load.
+template <typename T, int V>
+__device__ __forceinline__ void miss_load_rows(const T *__restrict__ col, i64 i, i64 N, bool whole, double (&x)[V]) {
+    if (whole) {
+        const Pack<T, V> p = ld_pack_nt<T, V>(col + i);
+#pragma unroll
+        for (int j = 0; j < V; ++j) x[j] = (double)p.v[j];
+    } else {
+#pragma unroll
+        for (int j = 0; j < V; ++j) x[j] = (i + j < N) ? (double)col[i + j] : 0.0;
+    }
+}
+
+// the cell policy of the fit: the cell as it was loaded
+struct MissCellAsLoaded {
+    const double *__restrict__ w;
+    __device__ __forceinline__ double factor(i64 k) const { return w[k]; }
+    template <int U, int V>
+    __device__ __forceinline__ void apply(double (&)[U][V], i64, i64, int) const {}
+};
+
+// the column lanes of a row meet in LDS in the order of c; the lanes c == 0 leave with the sums of their rows
+template <int NACC, int V>
+__device__ __forceinline__ void miss_lanes_meet(double (&acc)[NACC][V], int RL, int CL, int r, int c) {
+    __shared__ double sm[WG][NACC * V];
+    if (CL == 1) return;
+#pragma unroll
+    for (int v = 0; v < V; ++v)
+#pragma unroll
+        for (int n = 0; n < NACC; ++n) sm[threadIdx.x][NACC * v + n] = acc[n][v];
+    __syncthreads();
+    if (c != 0) return;
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+        double s[NACC] = {};
+        for (int cc = 0; cc < CL; ++cc)
+#pragma unroll
+            for (int n = 0; n < NACC; ++n) s[n] += sm[r + cc * RL][NACC * v + n];
+#pragma unroll
+        for (int n = 0; n < NACC; ++n) acc[n][v] = s[n];
+    }
+}
+
+// One lane's columns k, k + CL, ... in batches of U for as long as a whole batch lies below ke; returns the first column left.
+// U = 1 is the tail loop.
+template <typename T, int V, int U, int NACC, typename Cell>
+__device__ __forceinline__ i64 miss_lane_batches(const T *__restrict__ X, i64 ldx, i64 N, i64 i0, bool whole, i64 k, i64 ke, int CL,
+                                                 const Cell &cell, double (&acc)[NACC][V]) {
+    for (; k + (i64)(U - 1) * CL < ke; k += (i64)U * CL) {
+        double x[U][V], wk[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            miss_load_rows<T, V>(X + (k + (i64)u * CL) * ldx, i0, N, whole, x[u]);
+            wk[u] = cell.factor(k + (i64)u * CL);
+        }
+        cell.apply(x, i0, k, CL);
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int v = 0; v < V; ++v) {
+                miss_obs_xw(x[u][v], wk[u], acc[0][v], acc[1][v]);
+                if constexpr (NACC == 4) miss_obs_xx(x[u][v], acc[2][v], acc[3][v]);
+            }
+    }
+    return k;
+}
+
+// One lane's walk and the meet.  True for the lanes that hold the sums of rows i0 .. i0 + V - 1 of this K range in acc.
+template <typename T, int V, int U, int NACC, bool PADDED, typename Cell>
+__device__ __forceinline__ bool miss_row_walk(const T *__restrict__ X, i64 ldx, i64 N, int K, int lrl, int kper, const Cell &cell,
+                                              double (&acc)[NACC][V], i64 &i0) {
+    static_assert(NACC == 2 || NACC == 4, "num, den and, for the diagnostics, q and the count");
+    const int RL = 1 << lrl, CL = WG >> lrl;
+    const int r = threadIdx.x & (RL - 1), c = threadIdx.x >> lrl;
+    i0 = ((i64)blockIdx.x * RL + r) * V;
+    const i64 kb = (i64)blockIdx.y * kper;
+    const i64 ke = kb + kper < K ? kb + kper : K;
+#pragma unroll
+    for (int n = 0; n < NACC; ++n)
+#pragma unroll
+        for (int v = 0; v < V; ++v) acc[n][v] = 0.0;
+    if (PADDED ? i0 < N : i0 + V <= N) {
+        const i64 k = miss_lane_batches<T, V, U>(X, ldx, N, i0, true, kb + c, ke, CL, cell, acc);
+        miss_lane_batches<T, V, 1>(X, ldx, N, i0, true, k, ke, CL, cell, acc);
+    } else if (i0 < N) {  // the lanes of the one row pack that straddles N: the same walk with element loads
+        const i64 k = miss_lane_batches<T, V, U>(X, ldx, N, i0, false, kb + c, ke, CL, cell, acc);
+        miss_lane_batches<T, V, 1>(X, ldx, N, i0, false, k, ke, CL, cell, acc);
+    }
+    miss_lanes_meet<NACC, V>(acc, RL, CL, r, c);
+    return c == 0;
+}
+
 //   tpart == nullptr (one K range)  t[i] = num / den
 //   else                            tpart[blockIdx.y][i] = {num, den}; miss_row_finish_kernel adds the ranges in order
-// ------------------------------------------------------------------------------------------------------------------------------
 template <typename T, int V>
 __device__ __forceinline__ void miss_row_body(const T *__restrict__ X, i64 ldx, i64 N, int K, const double *__restrict__ w, int lrl,
                                               int kper, double *__restrict__ t, double *__restrict__ tpart,
                                               const int *__restrict__ stop) {
-    __shared__ double sm[WG][2 * V];
     if (stop && *stop) return;
-    const int RL = 1 << lrl, CL = WG >> lrl;
-    const int r = threadIdx.x & (RL - 1), c = threadIdx.x >> lrl;
-    const i64 i0 = ((i64)blockIdx.x * RL + r) * V;
-    const i64 kb = (i64)blockIdx.y * kper;
-    const i64 ke = kb + kper < K ? kb + kper : K;
-    double an[V], ad[V];
-#pragma unroll
-    for (int j = 0; j < V; ++j) an[j] = ad[j] = 0.0;
-    if (i0 < N) {
-        constexpr int U = 8;  // loads in flight per lane per batch
-        i64 k = kb + c;
-        for (; k + (i64)(U - 1) * CL < ke; k += (i64)U * CL) {
-            Pack<T, V> x[U];
-            double wk[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                x[u] = ld_pack_nt<T, V>(X + i0 + (k + (i64)u * CL) * ldx);
-                wk[u] = w[k + (i64)u * CL];
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int j = 0; j < V; ++j) {
-                    const double xd = (double)x[u].v[j];
-                    const bool ob = xd == xd;
-                    an[j] = ob ? fma(xd, wk[u], an[j]) : an[j];
-                    ad[j] = ob ? fma(wk[u], wk[u], ad[j]) : ad[j];
-                }
-        }
-        for (; k < ke; k += CL) {
-            const double wk = w[k];
-            const Pack<T, V> x = ld_pack_nt<T, V>(X + i0 + k * ldx);
-#pragma unroll
-            for (int j = 0; j < V; ++j) {
-                const double xd = (double)x.v[j];
-                const bool ob = xd == xd;
-                an[j] = ob ? fma(xd, wk, an[j]) : an[j];
-                ad[j] = ob ? fma(wk, wk, ad[j]) : ad[j];
-            }
-        }
-    }
-    if (CL > 1) {
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-            sm[threadIdx.x][2 * j] = an[j];
-            sm[threadIdx.x][2 * j + 1] = ad[j];
-        }
-        __syncthreads();
-        if (c == 0) {
-#pragma unroll
-            for (int j = 0; j < V; ++j) {
-                double sn = 0.0, sd = 0.0;
-                for (int cc = 0; cc < CL; ++cc) {
-                    sn += sm[r + cc * RL][2 * j];
-                    sd += sm[r + cc * RL][2 * j + 1];
-                }
-                an[j] = sn;
-                ad[j] = sd;
-            }
-        }
-    }
-    if (c != 0) return;
+    double acc[2][V];
+    i64 i0;
+    if (!miss_row_walk<T, V, 8, 2, true>(X, ldx, N, K, lrl, kper, MissCellAsLoaded{w}, acc, i0)) return;
 #pragma unroll
     for (int j = 0; j < V; ++j)
         if (i0 + j < N) {
             if (tpart) {
-                st_pack<double, 2>(tpart + ((i64)blockIdx.y * N + i0 + j) * 2, Pack<double, 2>{{an[j], ad[j]}});
+                st_pack<double, 2>(tpart + ((i64)blockIdx.y * N + i0 + j) * 2, Pack<double, 2>{{acc[0][j], acc[1][j]}});
             } else {
-                t[i0 + j] = miss_quot(an[j], ad[j]);
+                t[i0 + j] = miss_quot(acc[0][j], acc[1][j]);
             }
         }
 }
@@ -255,36 +307,49 @@ __global__ __launch_bounds__(WG) void miss_row_kernel(const T *__restrict__ X, i
     miss_row_body<T, V>(X, ldx, N, K, w, lrl, kper, t, tpart, stop);
 }
 
-// t[i] = num / den over the S ranges.  A workgroup owns MISS_RF_ROWS rows; range lane sl adds the ranges sl, sl + SL, ... in order
-// (SL = WG / MISS_RF_ROWS, four loads in flight), then the SL lanes of a row meet in LDS in the order of sl.
-constexpr int MISS_RF_ROWS = 16;
-__device__ __forceinline__ void miss_row_finish_body(const double *__restrict__ tpart, int S, i64 N, double *__restrict__ t,
-                                                     const int *__restrict__ stop) {
+// The S ranges of a row, NACC values each.  A workgroup owns MISS_RF_ROWS (miss_layout.hpp) rows; range lane sl adds the ranges
+// sl, sl + SL, ... in order (SL = WG / MISS_RF_ROWS, four loads in flight: one dependent chain of S loads per row cost more than
+// the sweep), then the SL lanes of a row meet in LDS in the order of sl.  True for the lane that holds the sums of row i.
+template <int NACC>
+__device__ __forceinline__ bool miss_ranges_sum(const double *__restrict__ part, int S, i64 N, double (&sum)[NACC], i64 &i) {
     constexpr int RR = MISS_RF_ROWS, SL = WG / RR;
-    __shared__ double sm[SL][RR][2];
-    if (stop && *stop) return;
+    __shared__ double sm[SL][RR][NACC];
     const int ri = threadIdx.x % RR, sl = threadIdx.x / RR;
-    const i64 i = (i64)blockIdx.x * RR + ri;
-    double num = 0.0, den = 0.0;
+    i = (i64)blockIdx.x * RR + ri;
+#pragma unroll
+    for (int n = 0; n < NACC; ++n) sum[n] = 0.0;
     if (i < N) {
 #pragma unroll 4
         for (int s = sl; s < S; s += SL) {
-            const Pack<double, 2> v = ld_pack<double, 2>(tpart + ((i64)s * N + i) * 2);
-            num += v.v[0];
-            den += v.v[1];
+            const double *p = part + ((i64)s * N + i) * NACC;
+#pragma unroll
+            for (int n = 0; n < NACC; n += 2) {
+                const Pack<double, 2> v = ld_pack<double, 2>(p + n);
+                sum[n] += v.v[0];
+                sum[n + 1] += v.v[1];
+            }
         }
     }
-    sm[sl][ri][0] = num;
-    sm[sl][ri][1] = den;
-    __syncthreads();
-    if (sl != 0 || i >= N) return;
-    num = den = 0.0;
 #pragma unroll
-    for (int q = 0; q < SL; ++q) {
-        num += sm[q][ri][0];
-        den += sm[q][ri][1];
+    for (int n = 0; n < NACC; ++n) sm[sl][ri][n] = sum[n];
+    __syncthreads();
+    if (sl != 0 || i >= N) return false;
+#pragma unroll
+    for (int n = 0; n < NACC; ++n) {
+        sum[n] = 0.0;
+#pragma unroll
+        for (int q = 0; q < SL; ++q) sum[n] += sm[q][ri][n];
     }
-    t[i] = miss_quot(num, den);
+    return true;
+}
+
+// t[i] = num / den over the S ranges
+__device__ __forceinline__ void miss_row_finish_body(const double *__restrict__ tpart, int S, i64 N, double *__restrict__ t,
+                                                     const int *__restrict__ stop) {
+    if (stop && *stop) return;
+    double sum[2];
+    i64 i;
+    if (miss_ranges_sum<2>(tpart, S, N, sum, i)) t[i] = miss_quot(sum[0], sum[1]);
 }
 __global__ __launch_bounds__(WG) void miss_row_finish_kernel(const double *__restrict__ tpart, int S, i64 N, double *__restrict__ t,
                                                              const int *__restrict__ stop) {

@@ -160,7 +160,7 @@ int xdiag_device(pls_hip_context *c, const T *X, i64 ldx, i64 N, i64 n_total, in
                 CHK(ensure(c, c->part, (size_t)G * nc * 8));
                 part = (double *)c->part.p;
             }
-            hipLaunchKernelGGL(plsk::xdiag_score_stats_kernel, dim3(G), blk, (size_t)(plsk::WG / plsk::WAVE) * nc * 8, c->stream, Sd, ldsd,
+            hipLaunchKernelGGL(plsk::xdiag_score_stats_kernel<true>, dim3(G), blk, (size_t)(plsk::WG / plsk::WAVE) * nc * 8, c->stream, Sd, ldsd,
                                N, c_lo, c_hi, copy_s ? (float *)S : nullptr, lds, part);
             LAUNCH_CHECK(c);
             if (need_sst) CHK(launch_reduce(c, part, G, nc, nullptr, 0, red + A + 1 + c_lo, LP));

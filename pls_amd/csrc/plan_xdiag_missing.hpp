@@ -50,7 +50,7 @@ int xdiag_missing_device(pls_hip_context *c, const T *X, i64 ldx, i64 N, int K, 
         LAUNCH_CHECK(c);
     } else {
         double *part = (double *)(ws + g.o_part);
-        const dim3 grid((unsigned)g.nrb, (unsigned)g.S), gfin((unsigned)((N + plsk::XDM_RF_ROWS - 1) / plsk::XDM_RF_ROWS));
+        const dim3 grid((unsigned)g.nrb, (unsigned)g.S), gfin((unsigned)((N + plsk::MISS_RF_ROWS - 1) / plsk::MISS_RF_ROWS));
         for (int a = 0; a < npass; ++a) {
             const int last = a == A ? 1 : 0;
             const double *wa = last ? nullptr : W + (i64)a * K;
@@ -79,7 +79,8 @@ int xdiag_missing_device(pls_hip_context *c, const T *X, i64 ldx, i64 N, int K, 
         double *part = (double *)c->part.p;
         {
             Scope s(c, PLS_HIP_FAM_SMALL, N * 8);
-            hipLaunchKernelGGL(plsk::xdm_colsum_kernel, dim3(G), blk, (size_t)(plsk::WG / plsk::WAVE) * 8, c->stream, (const double *)q0, N, N, 1, part);
+            hipLaunchKernelGGL(plsk::xdiag_score_stats_kernel<false>, dim3(G), blk, (size_t)(plsk::WG / plsk::WAVE) * 8, c->stream,
+                               (const double *)q0, N, N, 0, 1, (float *)nullptr, (i64)0, part);
             LAUNCH_CHECK(c);
         }
         CHK(launch_reduce(c, part, G, 1, nullptr, 0, red, LP));
@@ -87,8 +88,8 @@ int xdiag_missing_device(pls_hip_context *c, const T *X, i64 ldx, i64 N, int K, 
             const int nc = std::min(A, c_lo + CH) - c_lo;
             {
                 Scope s(c, PLS_HIP_FAM_SMALL, N * (i64)nc * 8);
-                hipLaunchKernelGGL(plsk::xdm_colsum_kernel, dim3(G), blk, (size_t)(plsk::WG / plsk::WAVE) * nc * 8, c->stream,
-                                   (const double *)(Qd + (i64)c_lo * ldqd), ldqd, N, nc, part);
+                hipLaunchKernelGGL(plsk::xdiag_score_stats_kernel<false>, dim3(G), blk, (size_t)(plsk::WG / plsk::WAVE) * nc * 8,
+                                   c->stream, (const double *)(Qd + (i64)c_lo * ldqd), ldqd, N, 0, nc, (float *)nullptr, (i64)0, part);
                 LAUNCH_CHECK(c);
             }
             CHK(launch_reduce(c, part, G, nc, nullptr, 0, red + 1 + c_lo, LP));
@@ -105,8 +106,8 @@ int xdiag_missing_device(pls_hip_context *c, const T *X, i64 ldx, i64 N, int K, 
             }
             {
                 Scope s(c, PLS_HIP_FAM_SMALL, N * (i64)nc * 12);
-                hipLaunchKernelGGL(plsk::xdiag_score_stats_kernel, dim3(G), blk, (size_t)(plsk::WG / plsk::WAVE) * nc * 8, c->stream,
-                                   (const double *)Sd, ldsd, N, c_lo, c_hi, copy_s ? (float *)S : nullptr, lds, part);
+                hipLaunchKernelGGL(plsk::xdiag_score_stats_kernel<true>, dim3(G), blk, (size_t)(plsk::WG / plsk::WAVE) * nc * 8,
+                                   c->stream, (const double *)Sd, ldsd, N, c_lo, c_hi, copy_s ? (float *)S : nullptr, lds, part);
                 LAUNCH_CHECK(c);
             }
             if (need_sst) CHK(launch_reduce(c, part, G, nc, nullptr, 0, red + A + 1 + c_lo, LP));

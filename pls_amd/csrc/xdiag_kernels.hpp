@@ -220,8 +220,10 @@ __global__ __launch_bounds__(WG) void xdiag_split_finish_kernel(const double *__
     }
 }
 
-// part[g][c - c_lo] = sum over the group's rows of Sd[i, c]^2 (may be null); Sout (fp32 storage, may be null) = the scores
-// rounded.  One thread per row, grid-stride; dynamic LDS (WG/WAVE) * (c_hi - c_lo) doubles.
+// part[g][c - c_lo] = sum over the group's rows of Sd[i, c]^2 (SQUARE; else of Sd[i, c]: the Q columns of
+// pls_hip_x_diagnostics_missing) (may be null); Sout (fp32 storage, may be null) = the scores rounded.  One thread per row,
+// grid-stride; dynamic LDS (WG/WAVE) * (c_hi - c_lo) doubles.  The layout reduce_partials_kernel sums.
+template <bool SQUARE>
 __global__ __launch_bounds__(WG) void xdiag_score_stats_kernel(const double *__restrict__ Sd, i64 ldsd, i64 N, int c_lo,
                                                                int c_hi, float *__restrict__ Sout, i64 ldso,
                                                                double *__restrict__ part) {
@@ -236,7 +238,7 @@ __global__ __launch_bounds__(WG) void xdiag_score_stats_kernel(const double *__r
             const double s = (i < N) ? Sd[i + (i64)c * ldsd] : 0.0;
             if (Sout && i < N) Sout[i + (i64)c * ldso] = (float)s;
             if (part) {
-                const double tot = wave_sum(s * s);
+                const double tot = wave_sum(SQUARE ? s * s : s);
                 if (lane == 0) mine[c - c_lo] += tot;
             }
         }

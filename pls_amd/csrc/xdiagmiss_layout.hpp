@@ -8,11 +8,10 @@
 //   K <= XDM_TILE_BYTES / (8 XDM_RT_MIN) = 1024                 (a row of 8-row tiles fits)
 //   N >= XDM_RT_MIN num_cu                                      (8-row tiles alone give every CU one)
 //   rt = min(pow2 floor of XDM_TILE_BYTES / (8 K), pow2 floor of N / num_cu, XDM_RT_MAX): the rows shrink before CUs go idle
-// Streaming route (everything else): one read-only sweep per component in the geometry of miss_row_kernel -- RL = 1 << lrl row
-// lanes x CL = WG / RL column lanes, `vec` rows per lane -- with K split into S ranges of kper columns where the row blocks alone
-// do not fill the chip; the ranges of a row are added in index order by a finish kernel.
+// Streaming route (everything else): one read-only sweep per component, the row sweep of the fit with `vec` rows per lane; its
+// K split is miss_row_split of miss_layout.hpp, and the ranges of a row are added in index order by a finish kernel.
 #pragma once
-#include "xb_route.hpp"  // i64, WG
+#include "miss_layout.hpp"  // miss_row_split; i64, WG
 
 namespace plsk {
 
@@ -60,17 +59,11 @@ inline XdmGeom xdiagmiss_geom_of(i64 N, i64 K, i64 A, int es, int num_cu, bool a
         g.S = 1;
         g.kper = (int)K;
     } else {
-        const i64 nv = (N + g.vec - 1) / g.vec;
-        g.lrl = 0;
-        while ((1 << g.lrl) < WG && ((i64)1 << g.lrl) < nv) ++g.lrl;
-        const int RL = 1 << g.lrl, CL = WG >> g.lrl;
-        g.nrb = (nv + RL - 1) / RL;
-        const i64 smax = std::max<i64>(1, K / (8 * CL));  // at least 8 columns per lane of a range
-        const i64 S = std::min<i64>(std::min<i64>(std::max<i64>(1, (4 * (i64)num_cu) / g.nrb), smax), 65535);
-        i64 kper = (K + S - 1) / S;
-        kper += (-kper) & (CL - 1);
-        g.kper = (int)std::min<i64>(kper, ((i64)1 << 31) - 1);
-        g.S = (int)((K + g.kper - 1) / g.kper);
+        const MissRowSplit s = miss_row_split(N, K, g.vec, num_cu);
+        g.lrl = s.lrl;
+        g.nrb = s.nrb;
+        g.S = s.S;
+        g.kper = s.kper;
     }
     i64 at = 0;
     auto take = [&](i64 bytes) { const i64 o = at; at += (bytes + 15) & ~(i64)15; return o; };

@@ -2,7 +2,10 @@
 // tests/test_xdiag_missing_ref.py claims, the on-chip budget of the tile, the K split and the workspace.  Includes only that
 // header; tests/test_xdiagmiss_layout.py builds it with ASan + UBSan and feeds it the cases.
 // stdin: one case per line "name N K A es route rt" (route 0 resident / 1 streaming; rt 0 on the streaming route), 256 CUs.
-// stdout: per case and alignment "name aligned route rt S kper ws_bytes", then "swept <n>" for the shapes of the sweep below.
+// stdout: per case and alignment "name aligned route rt S kper ws_bytes split_S tail_lo tail_hi" (the last three: the K ranges of
+// miss_row_split at this shape and the fewest / most columns a lane owns in the last one), then "swept <n>" for the shapes of the
+// sweep below and "split <n>" for the shapes on which miss_geom_of and xdiagmiss_geom_of are held to miss_row_split
+// (miss_layout.hpp).
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -76,7 +79,12 @@ int main() {
             EXPECT(g.route != plsk::XDM_RESIDENT || g.rt == rt, "%s: claims %d tile rows, the header says %d", name, rt, g.rt);
             invariants(name, N, K, A, es, cu, al != 0, false);
             invariants(name, N, K, A, es, cu, al != 0, true);
-            std::printf("%s %d %d %d %d %d %lld\n", name, al, g.route, g.route == plsk::XDM_RESIDENT ? g.rt : 0, g.S, g.kper, (long long)g.ws_bytes);
+            // the columns a lane owns in the last K range of the row sweep at this shape (the split of the fit and, with K
+            // split or not, of the streaming route): lane c has ceil((left - c) / CL) of the `left` columns
+            const plsk::MissRowSplit s = plsk::miss_row_split(N, K, g.vec, cu);
+            const long long CL = plsk::WG >> s.lrl, left = K - (long long)(s.S - 1) * s.kper;
+            std::printf("%s %d %d %d %d %d %lld %d %lld %lld\n", name, al, g.route, g.route == plsk::XDM_RESIDENT ? g.rt : 0, g.S, g.kper,
+                        (long long)g.ws_bytes, s.S, left / CL, (left + CL - 1) / CL);
         }
     }
     // a sweep of shapes around the thresholds and far from them, several CU counts
@@ -97,5 +105,38 @@ int main() {
                         swept += 2;
                     }
     std::printf("swept %lld\n", swept);
+    // the K split of a row sweep is written once: the fit's geometry (16 / es rows per lane) and the streaming route's (16 / es or
+    // one row per lane) are miss_row_split's, the ranges cover K and a range is whole turns of the column lanes
+    long long split = 0;
+    std::vector<long long> rows;
+    for (long long n = 1; n <= 70; ++n) rows.push_back(n);
+    for (long long n = 255; n <= 260; ++n) rows.push_back(n);
+    for (long long n = 511; n <= 514; ++n) rows.push_back(n);
+    rows.push_back(5000);
+    const long long cols[] = {1, 7, 8, 9, 63, 64, 65, 513, 20011, 200000};
+    const int split_cus[] = {1, 64, 256};
+    for (long long n : rows)
+        for (long long k : cols)
+            for (int e = 4; e <= 8; e += 4)
+                for (int vec : {1, 16 / e})
+                    for (int c : split_cus) {
+                        const plsk::MissRowSplit s = plsk::miss_row_split(n, k, vec, c);
+                        const int CL = plsk::WG >> s.lrl;
+                        std::snprintf(name, sizeof(name), "split-%lldx%lld-es%d-vec%d-cu%d", n, k, e, vec, c);
+                        EXPECT((i64)(s.S - 1) * s.kper < k && k <= (i64)s.S * s.kper, "%s: %d ranges of %d columns", name, s.S, s.kper);
+                        EXPECT(s.kper % CL == 0, "%s: a range of %d columns for %d column lanes", name, s.kper, CL);
+                        const plsk::XdmGeom x = plsk::xdiagmiss_geom_of(n, k, k < 3 ? k : 3, e, c, vec > 1, true);
+                        EXPECT(x.vec == vec && x.lrl == s.lrl && x.nrb == s.nrb && x.S == s.S && x.kper == s.kper,
+                               "%s: the streaming route has {%d, %lld, %d, %d}, the split {%d, %lld, %d, %d}", name, x.lrl, (long long)x.nrb,
+                               x.S, x.kper, s.lrl, (long long)s.nrb, s.S, s.kper);
+                        if (vec > 1) {
+                            const plsk::MissGeom m = plsk::miss_geom_of(n, k, e, c);
+                            EXPECT(m.lrl == s.lrl && m.nrb == s.nrb && m.S == s.S && m.kper == s.kper,
+                                   "%s: the fit has {%d, %lld, %d, %d}, the split {%d, %lld, %d, %d}", name, m.lrl, (long long)m.nrb, m.S,
+                                   m.kper, s.lrl, (long long)s.nrb, s.S, s.kper);
+                        }
+                        ++split;
+                    }
+    std::printf("split %lld\n", split);
     return failures ? 1 : 0;
 }

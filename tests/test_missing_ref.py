@@ -47,7 +47,19 @@ CASES = {
     "5x12": (5, 12, 1, 2, 0.10, "f64"),
     "512x24": (512, 24, 1, 2, 0.10, "f64"),
     "513x24": (513, 24, 1, 2, 0.10, "f64"),
+    # the batch tails of the row sweep's lane walk (miss_row_walk: 8 columns in flight per lane, then a column at a time): the
+    # columns a lane owns in the LAST K range, by miss_row_split for 256 compute units and 16-byte packs.  Eight column lanes per
+    # row (nine ranges of 72 columns): 57 columns left = 7 or 8 per lane, 65 left = 8 or 9; N = 41 is no multiple of the pack.
+    # One column lane (ranges of 9, 8 and 9 columns): 7, 8 and 9 left; N = 601 is no multiple of the fp32 pack of 4.
+    "40x633": (40, 633, 1, 3, 0.10, "f64"),
+    "41x641": (41, 641, 1, 3, 0.10, "f64"),
+    "600x313": (600, 313, 1, 3, 0.10, "f64"),
+    "601x304-f32": (601, 304, 1, 3, 0.10, "f32"),
+    "602x306": (602, 306, 1, 3, 0.10, "f64"),
 }
+# name -> (fewest, most) columns a lane owns in the LAST K range of the row sweep, 256 compute units: what the comments above claim.
+# tests/test_xdiagmiss_layout.py holds miss_row_split (pls_amd/csrc/miss_layout.hpp) to it.
+TAILS = {"40x633": (7, 8), "41x641": (8, 9), "600x313": (7, 7), "601x304-f32": (8, 8), "602x306": (9, 9)}
 MULTI = tuple(n for n, c in CASES.items() if c[2] > 1)
 
 

@@ -6,15 +6,15 @@ x_k <- x_k - t_a P[k,a] on O,  q_{a+1} = sum_O x_k^2.  S[i,a] = t_a, Q[i,c-1] = 
 ssx = [sum_i q_0, column sums of Q], sst = column sums of S^2, nobs = |O|; tvar None: sst / (N - 1).
 tests/test_gpu_xdiag_missing.py and tests/test_xdiagmiss_layout.py take their cases, the yardstick and the bars from here.
 
-Cases: the twelve of tests/test_missing_ref.py (their data, W and P from their yardstick fit), and the smallest shapes on either side
+Cases: those of tests/test_missing_ref.py (their data, W and P from their yardstick fit), and the smallest shapes on either side
 of every threshold of xdiagmiss_geom_of (pls_amd/csrc/xdiagmiss_layout.hpp) on a device of 256 compute units, with data by the
 same recipe and W, P from fit_missing_ref.  Each case names the route and the tile rows it claims; tests/cpp/xdiagmiss_layout.cpp
-holds the header to that.
+holds the header to that.  The last five straddle the batch tails of the streaming sweep's lane walk.
 
 Self-checks of the yardstick:
   * its S equals scores_missing_ref; on the training X it equals the yardstick fit's T;
   * on the complete data Xc, with S = Xc R: Q, ssx and T2 equal the direct form F_c = Xc - S[:, :c] P[:, :c]^T;
-  * float64 against longdouble stays below 1e-13 on S, Q (whole matrix and worst row), T2 and ssx.  Measured for the twelve cases
+  * float64 against longdouble stays below 1e-13 on S, Q (whole matrix and worst row), T2 and ssx.  Measured for the cases
     of test_missing_ref: S <= 2.7e-15, Q <= 4.2e-16, worst row of Q (worst_row below) <= 1.5e-15; over all cases T2 <= 7.8e-15, ssx <= 3.9e-15;
   * the smallest Q / row sum of squares is 1.1e-3 over those cases: the residual is not a cancellation of leading digits.
 """
@@ -56,8 +56,21 @@ CASES.update({
     "8192x257": (8192, 257, 2, 0.10, "f64", RESIDENT, 16),
     "4096x512": (4096, 512, 2, 0.10, "f64", RESIDENT, 16),
     "4096x513": (4096, 513, 2, 0.10, "f64", RESIDENT, 8),
+    # the batch tails of the streaming sweep's lane walk (miss_row_walk: 4 columns in flight per lane, then a column at a time):
+    # the columns a lane owns in the LAST K range, by miss_row_split for 256 compute units and 16-byte packs.  Several column
+    # lanes per row: 25 columns left for 8 lanes = 3 or 4 per lane, 65 left for 16 lanes = 4 or 5; one column lane (ranges of 9
+    # columns): 3, 4 and 5 left.  N = 42, 601 and 603 are no multiples of the pack.  A = 7: the deflation chain takes its
+    # components four (two for fp32 packs) at a time, so the sweeps for a = 0 .. 7 see every group count and every remainder.
+    "40x601": (40, 601, 7, 0.10, "f64", STREAM, 0),
+    "42x641-f32": (42, 641, 7, 0.10, "f32", STREAM, 0),
+    "600x300": (600, 300, 7, 0.10, "f64", STREAM, 0),
+    "601x301-f32": (601, 301, 7, 0.10, "f32", STREAM, 0),
+    "603x302": (603, 302, 7, 0.10, "f64", STREAM, 0),
 })
-# The streaming route has the geometry of miss_row_kernel, whose thresholds the twelve cases sit on: one K range (67x19, 5x12)
+# name -> (fewest, most) columns a lane owns in the LAST K range of the streaming sweep, aligned layout, 256 compute units: what the
+# comments above claim.  tests/test_xdiagmiss_layout.py holds miss_row_split to it (the fit's cases: TAILS of test_missing_ref).
+TAILS = {"40x601": (3, 4), "42x641-f32": (4, 5), "600x300": (3, 3), "601x301-f32": (4, 4), "603x302": (5, 5)}
+# The streaming route has the geometry of miss_row_kernel, whose thresholds the first twelve cases sit on: one K range (67x19, 5x12)
 # against several (130x70, 33x20011), column lanes that meet in LDS (130x70) against none (257x33-m3), one row block (512x24)
 # against two (513x24; fp32: 1031x130-f32).
 
@@ -68,7 +81,7 @@ def _seed(name):
 
 @functools.lru_cache(maxsize=None)
 def xd_case(name):
-    """(X with NaN, X complete, dict(W, P, R, T) of the yardstick fit): read-only; the twelve cases of test_missing_ref as they are"""
+    """(X with NaN, X complete, dict(W, P, R, T) of the yardstick fit): read-only; the cases of test_missing_ref as they are"""
     N, K, A, frac, st, _, _ = CASES[name]
     if name in FIT_CASES:
         X, _, Xc = case_data(name)
