@@ -41,6 +41,46 @@
  * less than a round of 4 GB would take.  tests/test_gpu_history.py holds every entry point to this on one GPU;
  * INTEGRATION.md section K lists the state a handle does keep.
  *
+ * Stream order: every compute entry point works on the handle's stream (pls_hip_create, pls_hip_set_stream) and on nothing else
+ * a caller can observe.  A call either ENQUEUES -- it returns once its work is queued, without waiting for the device -- or
+ * COMPLETES -- it returns after its work has run, because the host has to read something back (a convergence word, the
+ * results of a host-memory call) or hands the device host memory of its own per round.  For both kinds:
+ *   1. no input is read before the work already queued on the handle's stream has run;
+ *   2. every output is complete for whatever is queued behind the call on that stream;
+ *   3. a call that enqueues does not wait for the device -- on a handle that has run the same call before: a first call
+ *      allocates or grows workspaces, the allocation may wait for the device, and growing a workspace that is in use waits
+ *      for the stream.
+ * Host arrays passed to a device-memory call (test_idx) may be reused as soon as the call returns.
+ *                                           PLS_HIP_MEM_DEVICE   PLS_HIP_MEM_HOST   ("-": the entry has device pointers only)
+ *   pls_hip_fit                             enqueues             completes
+ *   pls_hip_coefficients                    enqueues             completes
+ *   pls_hip_xb                              enqueues             completes
+ *   pls_hip_xty                             enqueues             -
+ *   pls_hip_deflate                         enqueues             -
+ *   pls_hip_colwise_z_scores                enqueues             -
+ *   pls_hip_sse_by_components               enqueues             -
+ *   pls_hip_model_sse                       enqueues             completes
+ *   pls_hip_cv_folds                        completes            completes          (the index list is the caller's host memory)
+ *   pls_hip_validation                      enqueues             completes
+ *   pls_hip_x_diagnostics                   enqueues             completes
+ *   pls_hip_fit_batch                       enqueues             completes
+ *   pls_hip_fit_resampled                   enqueues             completes
+ *   pls_hip_cv_press_batch                  completes            completes          (the index list)
+ *   pls_hip_fit_missing, M = 1              enqueues             completes
+ *   pls_hip_fit_missing, M > 1              completes            completes          (the host reads the convergence word)
+ *   pls_hip_cv_folds_missing                completes            completes          (the index list; the convergence word)
+ *   pls_hip_scores_missing                  enqueues             completes
+ *   pls_hip_x_diagnostics_missing           enqueues             completes
+ *   pls_hip_colwise_z_scores_missing        enqueues             completes
+ *   pls_hip_synth_x                         enqueues             -
+ *   pls_hip_synth_y                         enqueues             -
+ * pls_hip_set_stream and pls_hip_destroy wait for the work pending on the handle's stream first: a call left pending by either
+ * still finishes with its outputs right.  A host-memory call may follow a pending device-memory call of the same handle
+ * without a synchronisation in between.  A handle on a row-sharded group completes wherever a message's answer is read by the
+ * host; pls_hip_group_* run member streams and host threads of their own and are not covered by this table.
+ * tests/test_gpu_stream_order.py holds every row of the table, on every route of the entry, to all three points on one GPU;
+ * INTEGRATION.md section K lists the state that crosses streams.
+ *
  * No torch types, no C++ types, no exceptions cross this boundary; every entry point
  * returns a pls_hip_status and never calls exit().  There is NO CPU fallback: without a
  * gfx950 device every compute entry point fails with PLS_HIP_ERR_DEVICE.

@@ -13,6 +13,7 @@ by the HIP kernels behind the C-ABI.
 from __future__ import annotations
 
 import ctypes
+import functools
 import sys
 
 import numpy as np
@@ -190,6 +191,20 @@ def resample_se(Bm2, nrep: int, kind: str = "bootstrap"):
 # handle
 # ---------------------------------------------------------------------------------------------
 
+def _on_handle_stream(method):
+    """The method's own torch work -- conversions, copies, the allocation of its outputs -- runs on the HANDLE's stream, where the
+    library's kernels run, whatever torch's current stream is (include/pls_hip.h, "Stream order"): a handle made with
+    Handle(stream=s) and called under another current stream would otherwise race with its own temporaries."""
+    @functools.wraps(method)
+    def on_stream(self, *args, **kwargs):
+        st = self._tstream
+        if st is None or torch.cuda.current_stream(self.device).cuda_stream == self._stream_ptr:
+            return method(self, *args, **kwargs)
+        with torch.cuda.stream(st):
+            return method(self, *args, **kwargs)
+    return on_stream
+
+
 class Handle:
     """One pls_hip context: a device, a stream, its workspace and (optionally) a reducer."""
 
@@ -204,6 +219,15 @@ class Handle:
         L.check(self._lib.pls_hip_create(ctypes.byref(h), self.device, ctypes.c_void_p(stream or 0)))
         self.h = h
         self._keep = []  # objects the C side points at (callbacks, reduce buffers)
+        self._view_stream(stream)
+
+    def _view_stream(self, stream):
+        """torch's view of the handle's stream (None without a GPU): what _on_handle_stream runs the methods' torch work under"""
+        self._stream_ptr = int(stream or 0)
+        self._tstream = None
+        if torch is not None and torch.cuda.is_available():
+            self._tstream = (torch.cuda.ExternalStream(self._stream_ptr, device=self.device) if self._stream_ptr
+                             else torch.cuda.default_stream(self.device))
 
     def close(self):
         if getattr(self, "h", None):
@@ -226,6 +250,7 @@ class Handle:
 
     def set_stream(self, stream: int | None):
         L.check(self._lib.pls_hip_set_stream(self.h, ctypes.c_void_p(stream or 0)), self.h)
+        self._view_stream(stream)
 
     def synchronize(self):
         L.check(self._lib.pls_hip_synchronize(self.h), self.h)
@@ -248,6 +273,7 @@ class Handle:
     def _dt(self, x):
         return L.F64 if x.dtype == torch.float64 else L.F32
 
+    @_on_handle_stream
     def fit_device(self, X, Y, A: int, method: int = KERNEL_TYPE1, want_B: bool = True, out=None):
         """X (N,K), Y (N,M) column-major CUDA tensors of one dtype.  Enqueues the fit and
         returns dict(W,P,Q,R,T,B) of device tensors (column-major views).  `out`: a dict
@@ -292,6 +318,7 @@ class Handle:
         L.check(rc, self.h)
         return dict(W=W, P=P, Q=Q, R=R, T=T if method == KERNEL_TYPE1 else None, B=B)
 
+    @_on_handle_stream
     def xb(self, X, Bm):
         """X (N,K) @ Bm (K,C): fitted_values / scores product."""
         if _is_torch(X):
@@ -316,6 +343,7 @@ class Handle:
         L.check(rc, self.h)
         return out
 
+    @_on_handle_stream
     def coefficients(self, R, Q, c: int):
         if _is_torch(R):
             R = as_colmajor(R); Q = as_colmajor(Q)
@@ -338,6 +366,7 @@ class Handle:
         L.check(self._lib.pls_hip_coefficients(self.h, p(R), p(Q), K, M, A, c, L.MEM_HOST, p(B)), self.h)
         return B
 
+    @_on_handle_stream
     def xty(self, X, Y):
         X = as_colmajor(X); Y = as_colmajor(Y, X.dtype)
         N, K = X.shape
@@ -348,6 +377,7 @@ class Handle:
         self._last_inputs = (X, Y)
         return out
 
+    @_on_handle_stream
     def deflate(self, src, t, p, dst=None):
         src = as_colmajor(src)
         N, K = src.shape
@@ -360,6 +390,7 @@ class Handle:
         self._last_inputs = (src, t, p)
         return dst
 
+    @_on_handle_stream
     def colwise_z_scores(self, X, n_total: int | None = None, inplace: bool = False):
         """(Z, mean, sd) of a device matrix: colwise_z_scores of the reference (src/pls.cpp:107-111)."""
         X = as_colmajor(X)
@@ -372,6 +403,7 @@ class Handle:
         self._last_inputs = (X,)
         return Z, mean, sd
 
+    @_on_handle_stream
     def sse_by_components(self, S, Y, Q):
         """SSE (M x A) for 1..A components from the scores S = X R (one sweep)."""
         S = as_colmajor(S); Y = as_colmajor(Y, S.dtype)
@@ -386,6 +418,7 @@ class Handle:
         self._last_inputs = (S, Y, Q)
         return out
 
+    @_on_handle_stream
     def cv_folds(self, X, Y, A: int, test_idx):
         """Residuals of batched cross-validation folds (cv_LOO / cv_LSO of the reference in one launch).
         test_idx: (num_folds, test_size) integer array of held-out rows.  Returns E with shape (M, nobs, A),
@@ -422,6 +455,7 @@ class Handle:
         L.check(rc, self.h)
         return E.transpose(0, 2, 1)
 
+    @_on_handle_stream
     def validation(self, E):
         """(press, D, probw, ref) of cross-validation residuals E, shape (M, nobs, A) as cv_folds returns them
         (pls_hip_validation): press (M, A) = column sums of squares, ref (M,) int64 = 0-based column of the PRESS minimum,
@@ -452,6 +486,7 @@ class Handle:
                 self.h)
         return press, D, probw, ref
 
+    @_on_handle_stream
     def x_diagnostics(self, X, R, P, tvar=None, want=("Q", "T2", "ssx"), n_total: int | None = None):
         """X-space diagnostics of a model (R, P: K x A) on data X (N x K) for every component count 1..A
         (pls_hip_x_diagnostics).  `want` picks from "Q" (Q residuals, N x A), "T2" (Hotelling T^2, N x A), "S" (scores,
@@ -507,6 +542,7 @@ class Handle:
         L.check(rc, self.h)
         return out
 
+    @_on_handle_stream
     def fit_batch(self, X, Ys, M: int, A: int, want=("B", "Q", "tt", "ssy")):
         """Many response sets against one X (pls_hip_fit_batch): Ys is N x (nprob * M), problem b owning columns
         [b*M, (b+1)*M); every problem is the KERNEL_TYPE2 model of (X, Y_b) on the shared X^T X.  Returns a dict of the
@@ -549,6 +585,7 @@ class Handle:
         L.check(rc, self.h)
         return {k: _batch_view(k, v) for k, v in out.items()}
 
+    @_on_handle_stream
     def fit_resampled(self, X, Y, A: int, weights, want=("B0", "Bmean", "Bm2")):
         """The same (X, Y) fitted under many sets of non-negative row weights (pls_hip_fit_resampled): weights is N x nrep,
         replicate b the KERNEL_TYPE1 model of (diag(s) X, diag(s) Y) with s = sqrt(weights[:, b]) -- bootstrap_weights,
@@ -597,6 +634,7 @@ class Handle:
         L.check(rc, self.h)
         return {k: (v.transpose(0, 2, 1) if k in ("Q", "B") else v.T if k != "tt" else v) for k, v in out.items()}
 
+    @_on_handle_stream
     def cv_press_batch(self, X, Ys, M: int, A: int, test_idx, want=("PRESS", "ssy")):
         """Cross-validated fits of many response sets against one X, reduced to PRESS (pls_hip_cv_press_batch): Ys is
         N x (nprob * M) as in fit_batch, test_idx (num_folds, test_size) as in cv_folds, the same folds for every problem.
@@ -647,6 +685,7 @@ class Handle:
         return {k: v.transpose(*view[k]) for k, v in out.items()}
 
     # ---- X with missing values -----------------------------------------------------------------------
+    @_on_handle_stream
     def fit_missing(self, X, Y, A: int, want=("W", "P", "Q", "R", "T", "B", "iters")):
         """NIPALS fit of X whose NaN cells are missing values (pls_hip_fit_missing): every inner product runs over the
         observed cells only.  Y must be complete.  Returns a dict of the outputs `want` names -- W, P, R (K, A), Q (M, A), T
@@ -689,6 +728,7 @@ class Handle:
         full = dict(W=W, P=P, Q=Q, R=R, T=T, B=B, iters=iters)
         return {k: full[k] for k in _MISSING_OUT if k in want}
 
+    @_on_handle_stream
     def cv_folds_missing(self, X, Y, A: int, test_idx, want_iters: bool = False):
         """Residuals of cross-validation folds of X whose NaN cells are missing values (pls_hip_cv_folds_missing): fold f is
         fit_missing on all rows but test_idx[f], scores_missing on the held-out rows, E_c = Y_test - S[:, :c] Q[:, :c]^T.
@@ -724,6 +764,7 @@ class Handle:
             E = E.transpose(0, 2, 1)
         return (E, iters) if want_iters else E
 
+    @_on_handle_stream
     def scores_missing(self, X, W, P):
         """Scores of rows, new or training, that may have missing cells (pls_hip_scores_missing): sequential deflation with
         the model's W and P (K, A).  (N, A) in the dtype of X.  On complete rows it equals xb(X, R)."""
@@ -750,6 +791,7 @@ class Handle:
         L.check(rc, self.h)
         return S
 
+    @_on_handle_stream
     def x_diagnostics_missing(self, X, W, P, tvar=None, want=("Q", "T2", "ssx")):
         """X-space diagnostics of rows, new or training, that may have missing cells (pls_hip_x_diagnostics_missing): NaN in X
         marks a missing cell, W and P (K, A) are the model's own W and P as for scores_missing.  `want` picks from "Q" (Q
@@ -806,6 +848,7 @@ class Handle:
         L.check(rc, self.h)
         return out
 
+    @_on_handle_stream
     def z_scores_missing(self, X, inplace: bool = False):
         """(Z, mean, sd, nobs) over the observed cells of each column (pls_hip_colwise_z_scores_missing): sd with nobs - 1,
         NaN kept in Z.  A column with fewer than two observed cells, or a constant one, is NaN throughout."""
@@ -834,6 +877,7 @@ class Handle:
         L.check(rc, self.h)
         return Z, mean, sd, nobs
 
+    @_on_handle_stream
     def permutation_test(self, X, Y, A: int, nperm: int, perms=None, seed: int = 0, max_bytes: int = 1 << 30, cv=None):
         """Response-permutation (Y-randomisation) test: problem 0 is Y itself, problem b is Y[perms[b-1]] (rows permuted,
         the M responses of a row together), all fitted against the same X by fit_batch.  perms: (nperm, N) int64; drawn
@@ -895,6 +939,7 @@ class Handle:
         L.check(self._lib.pls_hip_get_reducer(self.h, ctypes.byref(on), ctypes.byref(rank), ctypes.byref(n)), self.h)
         return bool(on.value)
 
+    @_on_handle_stream
     def synth_x(self, row0: int, nrows: int, K: int, seed: int, dtype=None, device=None):
         dtype = dtype or torch.float64
         X = colmajor_empty(nrows, K, dtype, device or f"cuda:{self.device}")
@@ -902,6 +947,7 @@ class Handle:
                                           L.F64 if dtype == torch.float64 else L.F32), self.h)
         return X
 
+    @_on_handle_stream
     def synth_y(self, row0: int, nrows: int, M: int, seed: int, dtype=None, device=None):
         dtype = dtype or torch.float64
         Y = colmajor_empty(nrows, M, dtype, device or f"cuda:{self.device}")
