@@ -63,6 +63,7 @@
  *   pls_hip_cv_folds                        completes            completes          (the index list is the caller's host memory)
  *   pls_hip_validation                      enqueues             completes
  *   pls_hip_x_diagnostics                   enqueues             completes
+ *   pls_hip_var_diagnostics                 enqueues             -
  *   pls_hip_fit_batch                       enqueues             completes
  *   pls_hip_fit_resampled                   enqueues             completes
  *   pls_hip_cv_press_batch                  completes            completes          (the index list)
@@ -213,6 +214,8 @@ typedef enum {
  * KERNEL_TYPE2 / GRAM add one message of 8*K*K (X^T X); pls_hip_colwise_z_scores sends two
  * of 8*K, pls_hip_sse_by_components one of 8*A*M per range of component counts,
  * pls_hip_x_diagnostics exactly one of 8*(2*A+1) per call ([ssx (A+1), sst (A)], whichever outputs were asked for).
+ * pls_hip_var_diagnostics sends exactly one when it reads X (ssxk, sst, or VIP without tt is asked for) and none otherwise:
+ * 8*(A + K*(A+1)) values, [sst (A) | ssxk (K x (A+1), ld K)], with ssxk asked for, 8*A values, [sst (A)], without.
  * pls_hip_cv_folds sends, in this order: the partition (8*nranks: each rank's row count in
  * its own slot); on its batched route X^T X (8*K*K) and X^T Y (8*K*M) of all rows; the
  * held-out rows (8*rows*(K+M) per message of whole folds, rows*(K+M) capped at 2^20 unless a
@@ -434,6 +437,37 @@ PLS_HIP_API int pls_hip_x_diagnostics(pls_hip_handle h, const void *X, int64_t l
                                       int64_t K, int64_t A, const double *R, const double *P, const double *tvar,
                                       int dtype, int mem, double *Qres, int64_t ldq, double *T2, int64_t ldt2, void *S,
                                       int64_t lds, double *ssx, double *sst);
+
+/*
+ * Variable-space diagnostics of a model on data X (N x K, as given: no centring) for every component count c = 1..A: which
+ * predictors the model uses (VIP) and how much of each predictor it reproduces (the per-variable residual sums of squares).
+ * DEVICE pointers only.  W, R, P are K x A with ld K, Q is M x A with ld M, tt has A entries; all fp64.  With S = X R (fp64 inside
+ * the library for either storage dtype) and F_c = X - S[:, :c] P[:, :c]^T:
+ *   ssxk (K x (A+1), ld ldk >= K)  ssxk[k, 0] = sum_i X[i,k]^2, ssxk[k, c] = sum_i F_c[i,k]^2:  R^2 X of variable k with c
+ *                                  components = 1 - ssxk[k, c] / ssxk[k, 0]
+ *   sst  (A)                       sst[a] = sum_i S[i,a]^2 from this call's scores
+ *   VIP  (K x A, ld ldv >= K)      VIP[k, c-1] = sqrt(K * sum_{a<c} ssy_a W[k,a]^2 / ||w_a||^2 / sum_{a<c} ssy_a),
+ *                                  ssy_a = tau_a * sum_m Q[m,a]^2, tau = tt when tt is non-NULL, this call's sst otherwise
+ *                                  (tt = t_a^T t_a of the training scores, as pls_hip_fit returns them in T; a zero denominator
+ *                                  gives the NaN the formula gives)
+ * F_c is formed explicitly, component by component in fp64, and then squared (no expansion of the square: it cancels).
+ * Any output may be NULL and work nobody asked for is not done: VIP with tt given reads nothing N-sized (X may be NULL, N is
+ * ignored); sst alone, or VIP without tt, reads X once for the scores; ssxk reads X once for the scores and once more per 24
+ * component counts by the column sweep.  Nothing N x K is written.
+ * PLS_HIP_ERR_INVALID, before anything is written: an output asked for without the inputs its definition names (ssxk: X, R, P;
+ * sst: X, R; VIP: W, Q, and tt or X and R); N < 1 where X is needed (0 on a rank of a sharded handle); A < 1, A > K, A > 2^20,
+ * K > 2^30; M < 1 when VIP is asked for; ldx < N, ldk < K, ldv < K.
+ * Any ld >= rows, element-aligned pointers, both storage dtypes, fixed summation order without atomics: the bits are a function
+ * of the arguments, the alignment of X and the device's CU count.  The call only enqueues work on the handle's stream.
+ * Row-sharded handle (a reducer installed): a COLLECTIVE whenever X is needed, which follows from the arguments every rank
+ * shares.  [sst | ssxk] is summed over the ranks in one message (pls_hip_allreduce_fn), VIP is formed behind it, and every rank
+ * ends with identical bits.  VIP with tt given is local.
+ * Out of scope: pls_hip_group_* and the C++ PLS::Model; a host-memory form of this call (host callers upload; the Python layer
+ * does); NaN cells in X (a NaN spreads through its column and every score); selectivity ratio; contribution plots; control limits.
+ */
+PLS_HIP_API int pls_hip_var_diagnostics(pls_hip_handle h, const void *X, int64_t ldx, int64_t N, int64_t K, int64_t M, int64_t A,
+                                        const double *W, const double *R, const double *P, const double *Q, const double *tt,
+                                        int dtype, double *ssxk, int64_t ldk, double *VIP, int64_t ldv, double *sst);
 
 /*
  * Many response sets against ONE X: for every problem b = 0..nprob-1 the model Model::plsr(X, Y_b, KERNEL_TYPE2)

@@ -78,6 +78,8 @@ PROTOTYPES = [
     ("pls_hip_validation", _int, [_vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp]),
     ("pls_hip_x_diagnostics", _int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _int, _int, _vp, _i64, _vp, _i64,
                                      _vp, _i64, _vp, _vp]),
+    ("pls_hip_var_diagnostics", _int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _int, _vp, _i64, _vp, _i64,
+                                       _vp]),
     ("pls_hip_fit_batch", _int, [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     ("pls_hip_fit_resampled", _int, [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _int, _int,
                                      _vp, _vp, _vp, _vp, _vp, _vp]),

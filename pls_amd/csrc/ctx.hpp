@@ -42,6 +42,7 @@ struct pls_hip_context {
     DevBuf mX, mws, mit, mzo;  // pls_hip_fit_missing and its companions (plan_missing.hpp): the work copy of X, vectors and partials, host staging of iters and of [mean, sd, nobs]
     DevBuf mcv, mcvidx;  // pls_hip_cv_folds_missing (plan_missing_cv.hpp): the slabs of a round's folds (miss_layout.hpp) and the round's word, the test rows (iters are staged in mit)
     DevBuf xmws, xmon;  // pls_hip_x_diagnostics_missing (plan_xdiag_missing.hpp): scores, Q columns, range partials and slices (xdiagmiss_layout.hpp), host staging of nobs
+    DevBuf vdST, vdpart, vdred, vdsm;  // pls_hip_var_diagnostics (plan_vardiag.hpp): the row-contiguous scores, the row splits' partials of a range, the message, [||w||^2 | ssy | sst]
     i64 opt_missing_iters = 500;  // PLS_HIP_OPT_MISSING_ITERS
     int *mconv_host = nullptr;    // pinned: where the host reads the convergence word of the M > 1 loop
     i64 opt_val_lds_rows = -1;  // PLS_HIP_OPT_VALIDATION_LDS_ROWS; -1 = the device's own limit
@@ -201,6 +202,7 @@ struct pls_hip_context {
     SCRATCH(rsw) SCRATCH(rsB) SCRATCH(rsacc) SCRATCH(rsX) SCRATCH(rsY) SCRATCH(rsW) SCRATCH(rsoS)                                      \
     SCRATCH(mX) SCRATCH(mws) SCRATCH(mit) SCRATCH(mzo) SCRATCH(mcv) SCRATCH(mcvidx)                                                    \
     SCRATCH(xmws) SCRATCH(xmon)                                                                                                        \
+    SCRATCH(vdST) SCRATCH(vdpart) SCRATCH(vdred) SCRATCH(vdsm)                                                                         \
     SCRATCH(guard)
 
 namespace {

@@ -44,6 +44,44 @@ void xdiag_launch_sweep_t(pls_hip_context *c, dim3 grid, const T *X, i64 ldx, i6
                        xdiag_ap(A), c_lo, c_hi, xout, qout, ldq, slice, first, part);
 }
 
+// The score stage of xdiag_device and vardiag_device (plan_vardiag.hpp): Sd (N x A, ld *ldsd) = X R in fp64 whatever the storage
+// type -- launch_xb for fp64 storage, into S when the caller's own fp64 output takes them, xdiag_scores_kernel for fp32 storage.
+// N >= 1.  Uses c->xdS (the scores) and c->xdPT (R^T).
+template <typename T>
+int xdiag_scores(pls_hip_context *c, const T *X, i64 ldx, i64 N, int K, int A, const double *R, T *S, i64 lds, const double **Sd_out,
+                 i64 *ldsd_out) {
+    const double *Sd = nullptr;
+    i64 ldsd = 0;
+    if (std::is_same<T, double>::value && S) {
+        Sd = (const double *)S;
+        ldsd = lds;
+        int nss = 0;
+        CHK(launch_xb<double>(c, (const double *)X, ldx, N, K, R, K, A, (double *)S, lds, nullptr, &nss));
+    } else {
+        const i64 ldn = N + (N & 1);
+        CHK(ensure(c, c->xdS, (size_t)ldn * A * 8));
+        double *ws = (double *)c->xdS.p;
+        Sd = ws;
+        ldsd = ldn;
+        if (std::is_same<T, double>::value) {
+            int nss = 0;
+            CHK(launch_xb<double>(c, (const double *)X, ldx, N, K, R, K, A, ws, ldn, nullptr, &nss));
+        } else {
+            const bool wide = plsk::vec_ok((uintptr_t)X, ldx, sizeof(T), 2);
+            const double *RT = nullptr;
+            CHK(xdiag_transposed(c, R, K, A, &RT));
+            for (int c_lo = 0; c_lo < A; c_lo += XD_RANGE) {
+                const int c_hi = std::min(A, c_lo + XD_RANGE);
+                if (wide) CHK((xdiag_launch_scores<T, 2>(c, X, ldx, N, K, RT, A, c_lo, c_hi, ws, ldn)));
+                else CHK((xdiag_launch_scores<T, 1>(c, X, ldx, N, K, RT, A, c_lo, c_hi, ws, ldn)));
+            }
+        }
+    }
+    *Sd_out = Sd;
+    *ldsd_out = ldsd;
+    return PLS_HIP_OK;
+}
+
 // All pointers are device memory.  Any of Qres, T2, S, ssx, sst may be null; tvar null = derive it from this call's scores.
 // On a handle with a reducer the call sends exactly one message of RED_SLICES * (2A + 1) values, whatever was asked for.
 template <typename T>
@@ -64,33 +102,7 @@ int xdiag_device(pls_hip_context *c, const T *X, i64 ldx, i64 N, i64 n_total, in
     // ---- scores, fp64 whatever the storage type
     const double *Sd = nullptr;
     i64 ldsd = 0;
-    if (N > 0) {
-        if (std::is_same<T, double>::value && S) {
-            Sd = (const double *)S;
-            ldsd = lds;
-            int nss = 0;
-            CHK(launch_xb<double>(c, (const double *)X, ldx, N, K, R, K, A, (double *)S, lds, nullptr, &nss));
-        } else {
-            const i64 ldn = N + (N & 1);
-            CHK(ensure(c, c->xdS, (size_t)ldn * A * 8));
-            double *ws = (double *)c->xdS.p;
-            Sd = ws;
-            ldsd = ldn;
-            if (std::is_same<T, double>::value) {
-                int nss = 0;
-                CHK(launch_xb<double>(c, (const double *)X, ldx, N, K, R, K, A, ws, ldn, nullptr, &nss));
-            } else {
-                const bool wide = plsk::vec_ok((uintptr_t)X, ldx, sizeof(T), 2);
-                const double *RT = nullptr;
-                CHK(xdiag_transposed(c, R, K, A, &RT));
-                for (int c_lo = 0; c_lo < A; c_lo += XD_RANGE) {
-                    const int c_hi = std::min(A, c_lo + XD_RANGE);
-                    if (wide) CHK((xdiag_launch_scores<T, 2>(c, X, ldx, N, K, RT, A, c_lo, c_hi, ws, ldn)));
-                    else CHK((xdiag_launch_scores<T, 1>(c, X, ldx, N, K, RT, A, c_lo, c_hi, ws, ldn)));
-                }
-            }
-        }
-    }
+    if (N > 0) CHK(xdiag_scores<T>(c, X, ldx, N, K, A, R, S, lds, &Sd, &ldsd));
     // ---- the residual sweep: XD_RANGE component counts at a time
     if (need_sweep) {
         const bool wide = plsk::vec_ok((uintptr_t)X, ldx, sizeof(T), 2);

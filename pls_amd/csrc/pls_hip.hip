@@ -33,6 +33,7 @@
 #include "cv_kernels.hpp"
 #include "validation_kernels.hpp"
 #include "xdiag_kernels.hpp"
+#include "vardiag_kernels.hpp"
 #include "batch_kernels.hpp"
 #include "dual_kernels.hpp"
 #include "dual_cv_kernels.hpp"
@@ -60,6 +61,7 @@ using plsk::i64;
 #include "fit_graph.hpp"
 #include "plan_validation.hpp"
 #include "plan_xdiag.hpp"
+#include "plan_vardiag.hpp"
 #include "plan_stats.hpp"
 #include "plan_cv.hpp"
 #include "dual_round.hpp"
@@ -655,6 +657,27 @@ int pls_hip_x_diagnostics(pls_hip_handle h, const void *X, int64_t ldx, int64_t 
                                dsst);
     }));
     return hc.finish();
+}
+
+int pls_hip_var_diagnostics(pls_hip_handle h, const void *X, int64_t ldx, int64_t N, int64_t K, int64_t M, int64_t A, const double *W,
+                            const double *R, const double *P, const double *Q, const double *tt, int dtype, double *ssxk, int64_t ldk,
+                            double *VIP, int64_t ldv, double *sst) {
+    CHK(check_handle(h));
+    CHK(check_dtype(h, dtype));
+    const bool need_x = ssxk || sst || (VIP && !tt);  // (the same on every rank of a sharded handle: it decides the message)
+    const bool empty_member = (N == 0 && h->nranks > 1);  // an empty shard still takes part in the message
+    if (K < 1 || A < 1 || A > K || A > (1 << 20) || K > (1 << 30))
+        return fail(h, PLS_HIP_ERR_INVALID, "bad var_diagnostics arguments: need 1 <= A <= K, A <= 2^20, K <= 2^30");
+    if (need_x && (N < 0 || (N == 0 && !empty_member) || (N > 0 && !X) || ldx < std::max<i64>(N, 1) || !R))
+        return fail(h, PLS_HIP_ERR_INVALID, "var_diagnostics: ssxk, sst and VIP without tt need X (N >= 1, ldx >= N) and R");
+    if (ssxk && (!P || ldk < K)) return fail(h, PLS_HIP_ERR_INVALID, "var_diagnostics: ssxk needs P and ldk >= K");
+    if (VIP && (!W || !Q || M < 1 || ldv < K)) return fail(h, PLS_HIP_ERR_INVALID, "var_diagnostics: VIP needs W, Q, M >= 1 and ldv >= K");
+    if (!need_x && !VIP) return PLS_HIP_OK;
+    CHK(set_device(h));
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return vardiag_device<T>(h, (const T *)X, ldx, need_x ? N : 0, K, M, (int)A, W, R, P, Q, tt, ssxk, ldk, VIP, ldv, sst);
+    });
 }
 
 int pls_hip_fit_missing(pls_hip_handle h, const void *X, int64_t ldx, const void *Y, int64_t ldy, int64_t N, int64_t K, int64_t M,

@@ -543,6 +543,65 @@ class Handle:
         return out
 
     @_on_handle_stream
+    def var_diagnostics(self, X, W=None, R=None, P=None, Q=None, tt=None, want=("VIP", "ssxk")):
+        """Variable-space diagnostics of a model on data X (N x K) for every component count 1..A (pls_hip_var_diagnostics).
+        `want` picks from "VIP" (K x A: variable importance in projection; needs W, Q and either tt = t_a^T t_a of the training
+        scores or X and R, whose scores then stand in), "ssxk" (K x (A + 1): sum_i X[i,k]^2, then the residual sums of squares of
+        variable k after 1..A components -- R^2 X of the variable is 1 - ssxk[:, c] / ssxk[:, 0]; needs X, R, P) and "sst" (A:
+        column sums of squares of the scores of X; needs X, R); the result is a dict of those.  X may be None when only "VIP" is
+        asked for and tt is given.  Torch CUDA tensors are passed as they are and the call only enqueues; numpy inputs are
+        uploaded with torch and numpy arrays come back.  Row-sharded handle: a collective whenever X is needed."""
+        want = set(want)
+        bad = want - {"VIP", "ssxk", "sst"}
+        if bad:
+            raise L.PlsHipError(L.ERR_INVALID, f"var_diagnostics: unknown output(s) {sorted(bad)}")
+        given = [m for m in (X, W, R, P, Q) if m is not None]
+        on_dev = any(_is_torch(m) for m in given)
+        if not on_dev and not torch.cuda.is_available():
+            raise L.PlsHipError(L.ERR_DEVICE, "var_diagnostics: numpy inputs are uploaded with torch, which finds no device")
+        dev = next((m.device for m in given if _is_torch(m)), torch.device("cuda", self.device))
+        f64 = torch.float64
+
+        def mat(m):
+            """the K x A (M x A) model matrix m as fp64 on the device, its columns packed (ld = its row count)"""
+            if m is None:
+                return None
+            t = as_colmajor(m.to(f64) if _is_torch(m) else torch.as_tensor(_np_f(m, np.float64)).to(dev))
+            if _ld(t) != t.shape[0]:
+                t = colmajor_empty(t.shape[0], t.shape[1], f64, dev, ld=t.shape[0]).copy_(t)
+            return t
+        if X is not None and not _is_torch(X):
+            dt = np.float32 if np.asarray(X).dtype == np.float32 else np.float64
+            Xh = _np_f(X, dt)
+            X = colmajor_empty(Xh.shape[0], Xh.shape[1], torch.float32 if dt == np.float32 else f64, dev)
+            X.copy_(torch.from_numpy(np.ascontiguousarray(Xh)))
+        elif X is not None:
+            X = as_colmajor(X)
+        W, R, P, Q = mat(W), mat(R), mat(P), mat(Q)
+        shaped = next((m for m in (W, R, P) if m is not None), None)
+        if shaped is None:
+            raise L.PlsHipError(L.ERR_INVALID, "var_diagnostics: one of W, R, P must be given")
+        K, A = shaped.shape
+        N = X.shape[0] if X is not None else 0
+        M = Q.shape[0] if Q is not None else 0
+        tv = None if tt is None else torch.as_tensor(tt, dtype=f64).to(dev).contiguous()
+        out = {}
+        if "VIP" in want: out["VIP"] = colmajor_empty(K, A, f64, dev)
+        if "ssxk" in want: out["ssxk"] = colmajor_empty(K, A + 1, f64, dev)
+        if "sst" in want: out["sst"] = torch.empty(A, dtype=f64, device=dev)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        rc = self._lib.pls_hip_var_diagnostics(self.h, ptr(X), _ld(X) if X is not None else 1, N, K, M, A, ptr(W), ptr(R), ptr(P), ptr(Q),
+                                               ptr(tv), self._dt(X) if X is not None else L.F64, ptr(out.get("ssxk")),
+                                               _ld(out["ssxk"]) if "ssxk" in out else K, ptr(out.get("VIP")),
+                                               _ld(out["VIP"]) if "VIP" in out else K, ptr(out.get("sst")))
+        L.check(rc, self.h)
+        self._last_inputs = (X, W, R, P, Q, tv)
+        if on_dev:
+            return out
+        self.synchronize()
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
+    @_on_handle_stream
     def fit_batch(self, X, Ys, M: int, A: int, want=("B", "Q", "tt", "ssy")):
         """Many response sets against one X (pls_hip_fit_batch): Ys is N x (nprob * M), problem b owning columns
         [b*M, (b+1)*M); every problem is the KERNEL_TYPE2 model of (X, Y_b) on the shared X^T X.  Returns a dict of the
@@ -1373,6 +1432,31 @@ class Model:
         out = self.handle.x_diagnostics(X, R, P, tvar=tv, want=("Q", "T2", "ssx"))
         ssx = out["ssx"]
         return dict(Q=out["Q"], T2=out["T2"], R2X=1.0 - ssx[1:] / ssx[0])
+
+    # ---- variable-space diagnostics (no counterpart in the reference) -------------------------------------
+    def vip(self):
+        """K x A: the variable importance in projection of every predictor for 1..A components (Handle.var_diagnostics);
+        sum_k VIP[k, c-1]^2 = K, "VIP > 1" is the usual selection rule.  t_a^T t_a comes from T when the fit produced it
+        (KERNEL_TYPE1, missing=True -- sound for a missing-value model, whose T are the scores of its own fit): no pass over X.
+        After KERNEL_TYPE2 it comes from the scores of the training data, one pass."""
+        if self.T is not None:
+            T = self.T.to(torch.float64) if _is_torch(self.T) else np.asarray(self.T, dtype=np.float64)
+            return self.handle.var_diagnostics(None, W=self.W, Q=self.Q, tt=(T * T).sum(0), want=("VIP",))["VIP"]
+        return self.handle.var_diagnostics(self._X, W=self.W, R=self.R, Q=self.Q, want=("VIP",))["VIP"]
+
+    def r2x_by_variable(self, X_new=None):
+        """K x A: the share of sum_i X[i,k]^2 of predictor k that 1..A components reproduce, 1 - ssxk[:, c] / ssxk[:, 0] of
+        Handle.var_diagnostics.  X_new=None: the training data.  New rows must be preprocessed as the training data was.  A
+        model fitted with missing=True / plsr_missing: PLS_HIP_ERR_UNSUPPORTED (NaN cells are outside the column sweep)."""
+        if self._missing:
+            raise L.PlsHipError(L.ERR_UNSUPPORTED, "r2x_by_variable: not for a model fitted with missing=True")
+        X = self._X if X_new is None else X_new
+        R, P = self.R, self.P
+        if _is_torch(X) != _is_torch(R):
+            R, P = ((R.cpu().numpy(), P.cpu().numpy()) if _is_torch(R) else
+                    (torch.as_tensor(np.asarray(R), device=X.device), torch.as_tensor(np.asarray(P), device=X.device)))
+        ssxk = self.handle.var_diagnostics(X, R=R, P=P, want=("ssxk",))["ssxk"]
+        return 1.0 - ssxk[:, 1:] / ssxk[:, :1]
 
     def permutation_test(self, nperm: int, perms=None, seed: int = 0, max_bytes: int = 1 << 30, cv=None):
         """Handle.permutation_test on the model's own training data with the model's number of components: is the R^2 Y
